@@ -20,12 +20,27 @@ call pairs instead.
 Synthetic data: random-init AlphaZeroNet weights of the 128x10b architecture
 (seeded), random openings of 0..8 plies.
 
-Also reported (rank 0):
+A plain run sets up, warms up, times the K steps and prints the line: the
+headline figures plus what the timed region's own counters give (rank 0):
   roofline      the fused ResNet kernel: algorithmic FLOPs (342.3 MFLOP per
                 evaluated leaf, n_eval = rows of non-terminal leaves,
                 BASELINE.md) / its average HIP-event duration, vs the 2.5
                 PFLOP/s dense bf16 MFMA peak; traffic from profiles/ if a PMC
                 summary for this config exists, else null.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path returned
+for its last step (the caller's tensors of the last self-play move: actions,
+finished, features, policy) as DIR/<name>.npy in float32 (rank r > 0:
+DIR/<name>_rank<r>.npy). Weights, openings and the engine's random streams are
+seeded, so two runs with the same arguments dump the same arrays.
+
+--full adds everything that takes runs of its own (each has its own switch):
+  sustained     the same games continued through endgames and restarts
+  net_outputs   the net's value spread and priors on real positions
+  deep_tree     the engine with the self-play trained net
+  other_configs configs[3] and the per-GPU shard of configs[4]
+  latency       single-game latency through the drop-in MCTS
+  roofline.measured_ceiling from this box's own MFMA probe run
   cpu_baseline  the oracle C restatement of the reference search + torch-CPU
                 fp32 ResNet, 1 game (configs[0]), a fixed number of moves after
                 a fixed warm-up, torch threads = the CPUs this process may use.
@@ -59,6 +74,7 @@ PEAK_HBM_GBS = 8000.0  # MI355X HBM3E (MI355X_MICROARCH.md)
 # BASELINE.md "Published numbers for this path": the reference on 1x RTX 4090 +
 # 24-core CPU, 128x10b, history 8, 800 sims/move, 2 threads x 16 (README.md:25)
 PUBLISHED_SIMS_PER_S = 28000.0
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: the most one rank writes, over all its arrays
 
 
 def kernel_hash(kind: str) -> str:
@@ -441,9 +457,18 @@ def parse_args(argv: list[str]):
     ap.add_argument("--dry-run", action="store_true",
                     help="rank plumbing only: no GPU, no search (gloo, each step a fixed sleep)")
     ap.add_argument("--dry-step-ms", type=float, default=20.0, help="--dry-run: ms per step (rank r: x (1 + r))")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the sub-records that take runs of their own (sustained, "
+                         "net_outputs, deep_tree, other_configs, latency, the MFMA ceiling probe, cpu_baseline); "
+                         "a plain run only warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (actions, finished, features, policy "
+                         "of the last self-play move) as DIR/<name>.npy, float32")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU workload (a dry run computes nothing)")
     return args
 
 
@@ -564,7 +589,7 @@ class EngineWorkload:
 
     def step(self) -> None:
         self.b.search(self.net, sync=self.args.sync_search)  # enqueue only; the timed region syncs at its end
-        self.b.selfplay_move(temperature_moves=12, opening_moves=8, emit_targets=True)
+        self.last = self.b.selfplay_move(temperature_moves=12, opening_moves=8, emit_targets=True)
 
     def steps(self, n: int) -> None:
         """n steps: one multi-move self-play call (oamd_engine_selfplay_steps, the
@@ -575,8 +600,34 @@ class EngineWorkload:
             for _ in range(n):
                 self.step()
         else:
-            self.b.selfplay_steps(self.net, n, temperature_moves=12, opening_moves=8, emit_targets=True,
-                                  keep_all=False)
+            out = self.b.selfplay_steps(self.net, n, temperature_moves=12, opening_moves=8, emit_targets=True,
+                                        keep_all=False)
+            if n > 0:  # (no move writes the buffers of a 0-step call)
+                self.last = out
+
+    def dump_outputs(self, out_dir: str, rank: int) -> None:
+        """--dump-outputs: the last step's outputs as the caller of the timed
+        path received them ((G,) actions and finished flags, (G, 8, 1 + 2H, 8, 8)
+        target features, (G, 8, 65) target policies), one float32 .npy each
+        (9.5 MB at 256 games; the int32 actions / flags are exact in float32).
+        Past DUMP_MAX_BYTES in all (~1800 games) every array keeps the same
+        fixed, seeded sample of games, in ascending order."""
+        import numpy as np
+
+        if getattr(self, "last", None) is None:
+            raise SystemExit("bench.py: --dump-outputs needs at least one step (--steps or --warmup > 0)")
+        self.sync()
+        arrays = {name: t.detach().to("cpu", torch.float32).numpy() for name, t in self.last.items()}
+        games = self.args.games
+        per_game = sum(a.nbytes for a in arrays.values()) // games
+        keep = DUMP_MAX_BYTES // per_game
+        if keep < games:
+            rows = np.sort(np.random.default_rng(0).choice(games, keep, replace=False))
+            arrays = {name: np.ascontiguousarray(a[rows]) for name, a in arrays.items()}
+        d = Path(out_dir)
+        d.mkdir(parents=True, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(d / (f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), a)
 
     def sync(self) -> None:
         """torch.cuda.synchronize(), preceded by polling an event of the stream
@@ -689,8 +740,10 @@ def report(args, world: int, rank: int, backend: str, wl) -> None:
             wl.step()
     wl.sync()
     dt_max, own, m, cpu_s = run_window(args, wl, world, backend, args.steps)
+    if args.dump_outputs:
+        wl.dump_outputs(args.dump_outputs, rank)
     sustained = None
-    if m is not None and args.sustained_moves > 0:
+    if args.full and m is not None and args.sustained_moves > 0:
         # the engine's real workload: the same games played on through their
         # endgames (all-terminal batches, chain splitting) and restarts (the
         # roofline covers every launch; HIP events sample every 5th search)
@@ -757,6 +810,7 @@ def report(args, world: int, rank: int, backend: str, wl) -> None:
     result["host"] = host_budget(ranks)
     if m is not None:
         result.update(measured_fields(args, m, workload))
+    if m is not None and args.full:
         result["net_outputs"] = wl.prior_stats()
         if sustained is not None:
             result["sustained"] = sustained
@@ -767,7 +821,7 @@ def report(args, world: int, rank: int, backend: str, wl) -> None:
         if args.latency_moves > 0 and rank == 0:
             result["latency"] = latency_record(args, wl)
     # the MFMA ceiling on this box (rank 0's GPU), after every timed region
-    if m is not None and rank == 0 and args.ceiling_probe:
+    if args.full and m is not None and rank == 0 and args.ceiling_probe:
         rl = [(args.dtype, result["roofline"])] + [(v.get("dtype"), v["roofline"])
                                                    for v in result.get("other_configs", {}).values()]
         got = same_box_ceiling({d for d, _ in rl})
@@ -776,7 +830,7 @@ def report(args, world: int, rank: int, backend: str, wl) -> None:
                 with_ceiling(r, got[d], "this box: tools/mfma_ceiling.hip after the timed regions")
     # the CPU baseline on rank 0 at every world size, after every timed region;
     # the other ranks wait at a gloo barrier (blocked, not spinning)
-    if args.cpu_baseline_moves > 0 and (m is not None or args.dry_run):
+    if args.full and args.cpu_baseline_moves > 0 and (m is not None or args.dry_run):
         if rank == 0:
             dry = args.dry_run
             result["cpu_baseline"] = cpu_baseline(args.history, args.channels, args.blocks - 1, args.hidden,

@@ -263,3 +263,52 @@ def test_same_box_ceiling_parses_the_probe(tmp_path, monkeypatch):
     assert r["measured_ceiling"] == {"TFLOP_s": 2000.0, "source": "test", "frac_achieved": 0.9, "frac_executed": 0.825}
     exe.unlink()
     assert bench.same_box_ceiling({"bf16"}) == {}
+
+
+def test_full_and_dump_outputs_options():
+    """A plain run is the default: --full (the sub-records with runs of their
+    own) is off, --dump-outputs names a directory and is refused for a dry run
+    (which computes nothing to write)."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--dry-run", "--dump-outputs", "out"])
+
+
+def test_dump_outputs_writes_float32_and_samples_past_the_cap(tmp_path, monkeypatch):
+    """dump_outputs on a stand-in workload (host tensors): every output as
+    float32 .npy, values kept; past DUMP_MAX_BYTES every array keeps the same
+    seeded sample of games, the same one on every call."""
+    import types
+
+    import numpy as np
+    import torch
+
+    G = 12
+    last = {"actions": torch.arange(G, dtype=torch.int32) - 1, "finished": torch.zeros(G, dtype=torch.int32),
+            "features": torch.arange(G * 8 * 5 * 64, dtype=torch.float32).reshape(G, 8, 5, 8, 8),
+            "policy": torch.rand((G, 8, 65), generator=torch.Generator().manual_seed(0))}
+    wl = types.SimpleNamespace(last=last, args=types.SimpleNamespace(games=G), sync=lambda: None)
+    bench.EngineWorkload.dump_outputs(wl, tmp_path / "all", 0)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").glob("*.npy")}
+    assert sorted(got) == sorted(last)
+    for k, t in last.items():
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], t.numpy().astype(np.float32))
+    per_game = sum(a.nbytes for a in got.values()) // G
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 5 * per_game + 3)
+    bench.EngineWorkload.dump_outputs(wl, tmp_path / "s1", 0)
+    bench.EngineWorkload.dump_outputs(wl, tmp_path / "s2", 1)
+    s1 = {p.stem: np.load(p) for p in (tmp_path / "s1").glob("*.npy")}
+    s2 = {p.stem: np.load(p) for p in (tmp_path / "s2").glob("*.npy")}
+    assert sorted(s2) == sorted(k + "_rank1" for k in s1)
+    assert sum(a.nbytes for a in s1.values()) <= 5 * per_game + 3
+    rows = (s1["actions"] + 1).astype(int)  # actions[g] = g - 1: the sampled games
+    assert len(rows) == 5 and list(rows) == sorted(set(rows))
+    for k, t in last.items():
+        assert np.array_equal(s1[k], t.numpy().astype(np.float32)[rows])
+        assert np.array_equal(s1[k], s2[k + "_rank1"])
+    wl.last = None
+    with pytest.raises(SystemExit):
+        bench.EngineWorkload.dump_outputs(wl, tmp_path / "none", 0)

@@ -74,7 +74,7 @@ def _check_line(out: dict, world: int, steps: int, step_ms: float, games: int) -
     assert abs(out["value"] - world * games * 800 * steps / dt) <= 1e-3 * out["value"] + 0.1
     assert "REHEARSAL" not in out["config"]["parallelism"] and out["config"]["backend"] == "gloo"
     assert "roofline" not in out
-    # the CPU baseline rides on every world size's line (rank 0, after the
+    # with --full the CPU baseline rides on every world size's line (rank 0, after the
     # timed regions, the other ranks parked at a gloo barrier); a dry run
     # times one move of it
     cb = out["cpu_baseline"]
@@ -87,7 +87,7 @@ def _check_two_rank_line(out: dict, steps: int, step_ms: float, games: int) -> N
 
 
 def test_bare_bench_gpus2_starts_its_own_ranks():
-    r = _run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1",
+    r = _run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--steps", "3", "--warmup", "1",
               "--games", "4", "--dry-step-ms", "30"])
     assert "starting 2 ranks" in r.stderr
     _check_two_rank_line(_one_line(r), 3, 30.0, 4)
@@ -96,7 +96,8 @@ def test_bare_bench_gpus2_starts_its_own_ranks():
 def test_driver_launch_gpus2():
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
               "--master-addr=127.0.0.1", f"--master-port={_free_port()}", BENCH,
-              "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "0", "--games", "8", "--dry-step-ms", "25"])
+              "--gpus", "2", "--dry-run", "--full", "--steps", "2", "--warmup", "0", "--games", "8",
+              "--dry-step-ms", "25"])
     assert "starting" not in r.stderr  # under a launcher bench.py starts nothing itself
     _check_two_rank_line(_one_line(r), 2, 25.0, 8)
 
@@ -107,7 +108,8 @@ def test_driver_launch_gpus8_dry_run():
     aggregate rate, the host budget and the CPU baseline at world size 8."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
               "--master-addr=127.0.0.1", f"--master-port={_free_port()}", BENCH,
-              "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "0", "--games", "256", "--dry-step-ms", "15"],
+              "--gpus", "8", "--dry-run", "--full", "--steps", "2", "--warmup", "0", "--games", "256",
+              "--dry-step-ms", "15"],
              timeout=600)
     _check_line(_one_line(r), 8, 2, 15.0, 256)
 
@@ -121,6 +123,7 @@ def test_driver_launch_gpus1_joins_a_process_group():
     out = _one_line(r)
     assert out["n_gpus"] == 1 and out["config"]["backend"] == "gloo"
     assert [x["rank"] for x in out["config"]["ranks"]] == [0]
+    assert "cpu_baseline" not in out  # a plain run times its steps only; the baseline rides on --full
     # a bare world-1 run has no process group
     out = _one_line(_run([sys.executable, BENCH, "--dry-run", "--steps", "1", "--warmup", "0", "--games", "4",
                           "--dry-step-ms", "5"]))
