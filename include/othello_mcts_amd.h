@@ -287,6 +287,59 @@ int oamd_engine_random_openings(oamd_engine *e, int32_t max_moves, uint64_t seed
 /* The random-stream key of a game (DESIGN.md "Random streams"). */
 int oamd_engine_game_key(oamd_engine *e, int32_t game, uint64_t *key_host);
 
+/* Per-game search mask: active_dev (G) bytes, nonzero = the game is searched,
+ * moved by oamd_engine_selfplay_move and by oamd_engine_apply_actions; NULL =
+ * every game. A native search of an engine with no active game is a no-op
+ * (0 simulations, 0 evaluations). oamd_engine_reset reactivates the games it
+ * resets. */
+int oamd_engine_set_active(oamd_engine *e, const uint8_t *active_dev);
+
+/* ------------------------------------------------------------------------ */
+/* Arena: G head-to-head matches between two nets, all on the device.        */
+/* Replaces play_game between two AlphaZeroPlayers (player.py:33-95,         */
+/* 177-259) as evaluation.py:15-90 runs it. Match g is game g of engine a     */
+/* (searched with net A) and game g of engine b (net B): two trees, one per   */
+/* player. Per ply only the side to move searches; the chosen action moves    */
+/* both roots, so each side keeps its subtree across both sides' moves. A     */
+/* forced pass is an ordinary ply (a one-child search, action 64).            */
+/* Both engines: same device, same number of games, same stream; their        */
+/* search configs may differ. OAMD_INVALID_ARGUMENT otherwise.                */
+/* ------------------------------------------------------------------------ */
+
+/* Reset both games of every match (random streams reseeded from each
+ * engine's creation seed), play the opening plies in both trees, count plies
+ * from 0 after the opening, and activate the side to move only (neither side
+ * if the opening ended the game). openings_dev: (G, opening_plies) int32
+ * actions, -1 = no more plies (an illegal ply ends that match's opening);
+ * NULL or opening_plies = 0: none. a_is_white_dev: (G) bytes, nonzero = net A
+ * plays white in that match; NULL = A plays black everywhere. */
+int oamd_arena_begin(oamd_engine *a, oamd_engine *b, const int32_t *openings_dev, int32_t opening_plies,
+                     const uint8_t *a_is_white_dev);
+/* One ply of every match from the roots as searched: the mover's tree gives
+ * the action (oamd_engine_selfplay_move's choice: temperature sampling while
+ * the ply < cfg->temperature_moves, else argmax with a random tie-break; one
+ * draw from the mover's game stream, none from the other side's), both roots
+ * move, and the next side to move is activated. cfg->opening_moves and
+ * cfg->emit_targets are ignored. Device outputs (may be NULL):
+ *   actions_dev (G): the action, -1 once the match is over;
+ *   finished_dev (G): UPDATED, never cleared (zero it before the first ply):
+ *     bits 0-1 = 1 draw, 2 black won, 3 white won once the match has ended,
+ *     bit 2 = a move came from an unexpanded root (uniform), bit 3 = a node
+ *     pool overflowed, bit 4 = the two trees' roots differ (the match stops);
+ *   discs_dev (G, 2): black and white discs, written when the match ends;
+ *   remaining_dev (1): decremented for every match that ends. */
+int oamd_arena_move(oamd_engine *a, oamd_engine *b, const oamd_selfplay_config *cfg, int32_t *actions_dev,
+                    int32_t *finished_dev, int32_t *discs_dev, int32_t *remaining_dev);
+/* Whole matches with native nets: per ply oamd_engine_search(a, net_a),
+ * oamd_engine_search(b, net_b) and oamd_arena_move, enqueued without a host
+ * wait in between; every 8 plies the number of running matches is read back
+ * and the call returns when it is 0 or after max_plies plies. actions_dev
+ * (max_plies, G), finished_dev (G) and discs_dev (G, 2) are required and
+ * initialised by the call; *plies_host = plies enqueued. */
+int oamd_arena_play(oamd_engine *a, oamd_net *net_a, oamd_engine *b, oamd_net *net_b,
+                    const oamd_selfplay_config *cfg, int32_t max_plies, int32_t *actions_dev,
+                    int32_t *finished_dev, int32_t *discs_dev, int32_t *plies_host);
+
 /* Timing accumulated over the timed oamd_engine_search calls (HIP events on
  * the launching streams; a query waits for the searches still in flight):
  * total ms spent in the NN kernel, number of NN launches, rows launched

@@ -1918,4 +1918,96 @@ int oamd_engine_game_key(oamd_engine* e, int32_t game, uint64_t* key) {
     return OAMD_OK;
 }
 
+int oamd_engine_set_active(oamd_engine* e, const uint8_t* active_dev) {
+    DeviceGuard dg(e->device);
+    launch_set_active(e->view(), active_dev, e->stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Arena: G matches between two engines (tree.hip k_arena_begin / k_arena_move)
+// ---------------------------------------------------------------------------
+static int arena_checks(const oamd_engine* a, const oamd_engine* b) {
+    if (!a || !b || a == b) return fail(OAMD_INVALID_ARGUMENT, "arena: expected two different engines");
+    if (a->device != b->device) return fail(OAMD_INVALID_ARGUMENT, "arena: engines on different devices");
+    if (a->G != b->G)
+        return fail(OAMD_INVALID_ARGUMENT, "arena: engines hold different numbers of games (" + std::to_string(a->G) +
+                                               " and " + std::to_string(b->G) + ")");
+    if (a->stream != b->stream) return fail(OAMD_INVALID_ARGUMENT, "arena: engines on different streams");
+    return OAMD_OK;
+}
+
+static int arena_cfg_checks(const oamd_selfplay_config* cfg) {
+    if (!cfg || cfg->temperature_moves < 0 || !(cfg->temperature > 0.0f))
+        return fail(OAMD_INVALID_ARGUMENT, "arena: bad move config");
+    return OAMD_OK;
+}
+
+int oamd_arena_begin(oamd_engine* a, oamd_engine* b, const int32_t* openings_dev, int32_t opening_plies,
+                     const uint8_t* a_is_white_dev) {
+    if (int rc = arena_checks(a, b)) return rc;
+    if (opening_plies < 0) return fail(OAMD_INVALID_ARGUMENT, "arena: opening_plies must be >= 0");
+    DeviceGuard dg(a->device);
+    launch_arena_begin(a->view(), b->view(), a->seed, b->seed, opening_plies > 0 ? openings_dev : nullptr,
+                       opening_plies, a_is_white_dev, a->stream);
+    LAUNCHCHK();
+    for (oamd_engine* e : {a, b}) {
+        e->step_phase = 0;
+        e->steps_left = 0;
+    }
+    return OAMD_OK;
+}
+
+int oamd_arena_move(oamd_engine* a, oamd_engine* b, const oamd_selfplay_config* cfg, int32_t* actions_dev,
+                    int32_t* finished_dev, int32_t* discs_dev, int32_t* remaining_dev) {
+    if (int rc = arena_checks(a, b)) return rc;
+    if (int rc = arena_cfg_checks(cfg)) return rc;
+    DeviceGuard dg(a->device);
+    SelfplayParams sp{cfg->temperature_moves, cfg->temperature, 0, 0};
+    launch_arena_move(a->view(), b->view(), sp, actions_dev, finished_dev, discs_dev, remaining_dev, a->stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* net_b, const oamd_selfplay_config* cfg,
+                    int32_t max_plies, int32_t* actions_dev, int32_t* finished_dev, int32_t* discs_dev,
+                    int32_t* plies_host) {
+    if (int rc = arena_checks(a, b)) return rc;
+    if (int rc = arena_cfg_checks(cfg)) return rc;
+    if (int rc = native_search_checks(a, net_a)) return rc;
+    if (int rc = native_search_checks(b, net_b)) return rc;
+    if (max_plies < 0) return fail(OAMD_INVALID_ARGUMENT, "arena: max_plies must be >= 0");
+    if (!actions_dev || !finished_dev || !discs_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "arena: actions, finished and discs buffers are required");
+    DeviceGuard dg(a->device);
+    if (int rc = a->ensure_free_slots()) return rc;
+    const int G = a->G;
+    hipStream_t s = a->stream;
+    int32_t* remaining = a->remaining_dev;
+    // every byte 0xFF: action -1 in the plies that are never enqueued
+    if (max_plies > 0) HIPCHK(hipMemsetAsync(actions_dev, 0xFF, sizeof(int32_t) * (size_t)max_plies * G, s));
+    HIPCHK(hipMemsetAsync(finished_dev, 0, sizeof(int32_t) * G, s));
+    HIPCHK(hipMemsetAsync(discs_dev, 0, sizeof(int32_t) * 2 * G, s));
+    HIPCHK(hipMemsetAsync(remaining, 0, sizeof(int32_t), s));
+    launch_arena_count(a->view(), remaining, s);
+    LAUNCHCHK();
+    constexpr int kReadEvery = 8;  // plies between two reads of the matches still running
+    int ply = 0;
+    for (;;) {
+        HIPCHK(hipMemcpyAsync(a->remaining_host, remaining, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (a->remaining_host[0] <= 0 || ply >= max_plies) break;
+        for (int k = 0; k < kReadEvery && ply < max_plies; ++k, ++ply) {
+            // only the side to move of each match is active in its engine
+            if (int rc = oamd_engine_search(a, net_a, nullptr, nullptr)) return rc;
+            if (int rc = oamd_engine_search(b, net_b, nullptr, nullptr)) return rc;
+            if (int rc = oamd_arena_move(a, b, cfg, actions_dev + (size_t)ply * G, finished_dev, discs_dev, remaining))
+                return rc;
+        }
+    }
+    if (plies_host) *plies_host = ply;
+    return OAMD_OK;
+}
+
 }  // extern "C"

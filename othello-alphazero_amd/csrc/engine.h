@@ -49,8 +49,14 @@ struct GameState {
     int32_t cuts;      // ... and the chains split so far in this search
     int32_t moves_left;  // free-running self-play (k_tree_free): moves this game still plays in the call
     int32_t fresh;       // ... 1: its next round starts a new search
-    int32_t pad[2];
+    int32_t arena;       // arena match (k_arena_begin): 0 none, 1 net A plays black, 2 net A plays white
+    int32_t pad;
 };
+static_assert(sizeof(GameState) == 128, "GameState layout");
+
+// Arena status bits reported in `finished` beside the outcome (bits 0-1) and
+// the self-play driver's bits 2-3 (tree.hip k_arena_move)
+constexpr int32_t kArenaDesync = 16;
 
 // Packed NN input row (FW uint64 words): word 0 = meta, then (p1, p2) of the
 // leaf and its H-1 nearest ancestors, untransformed. meta bit 0 = player - 1,

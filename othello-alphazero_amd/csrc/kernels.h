@@ -42,6 +42,17 @@ void launch_self_play_data(const EngineView& E, int g, float* feat, float* pol, 
 void launch_selfplay_move(const EngineView& E, const SelfplayParams& sp, int g0, int ng, int32_t* actions,
                           int32_t* finished, float* feat, float* pol, hipStream_t s);
 void launch_random_openings(const EngineView& E, int max_moves, uint64_t seed, hipStream_t s);
+// Per-game search mask (active: G bytes on the device, nullptr = every game)
+void launch_set_active(const EngineView& E, const uint8_t* active, hipStream_t s);
+// Arena (tree.hip k_arena_begin / k_arena_move): match g = game g of engines A
+// and B (same G). begin resets both games, plays the opening plies in both
+// trees and activates the side to move; move plays one ply of every match;
+// count adds the matches still running to *remaining (zeroed by the caller).
+void launch_arena_begin(const EngineView& EA, const EngineView& EB, uint64_t seed_a, uint64_t seed_b,
+                        const int32_t* openings, int plies, const uint8_t* a_is_white, hipStream_t s);
+void launch_arena_count(const EngineView& EA, int32_t* remaining, hipStream_t s);
+void launch_arena_move(const EngineView& EA, const EngineView& EB, const SelfplayParams& sp, int32_t* actions,
+                       int32_t* finished, int32_t* discs, int32_t* remaining, hipStream_t s);
 // Free-running self-play (tree.hip k_tree_free): begin sets every game of the
 // group to play n_moves moves starting with a fresh search and counts them in
 // *remaining; each round runs one search round per game, a game's move in the

@@ -667,6 +667,34 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                  check(oamd_engine_game_key(e.h, game, &k));
                  return k;
              })
+        .def("set_active",
+             [](Engine& e, uintptr_t active) {
+                 check(oamd_engine_set_active(e.h, reinterpret_cast<const uint8_t*>(active)));
+             })
+        // arena (othello_mcts/arena.py): self = engine A, other = engine B
+        .def("arena_begin",
+             [](Engine& a, Engine& b, uintptr_t openings, int opening_plies, uintptr_t a_is_white) {
+                 check(oamd_arena_begin(a.h, b.h, reinterpret_cast<const int32_t*>(openings), opening_plies,
+                                        reinterpret_cast<const uint8_t*>(a_is_white)));
+             })
+        .def("arena_move",
+             [](Engine& a, Engine& b, int temperature_moves, float temperature, uintptr_t actions, uintptr_t finished,
+                uintptr_t discs, uintptr_t remaining) {
+                 oamd_selfplay_config c{temperature_moves, temperature, 0, 0};
+                 check(oamd_arena_move(a.h, b.h, &c, reinterpret_cast<int32_t*>(actions),
+                                       reinterpret_cast<int32_t*>(finished), reinterpret_cast<int32_t*>(discs),
+                                       reinterpret_cast<int32_t*>(remaining)));
+             })
+        .def("arena_play",
+             [](Engine& a, uintptr_t net_a, Engine& b, uintptr_t net_b, int temperature_moves, float temperature,
+                int max_plies, uintptr_t actions, uintptr_t finished, uintptr_t discs) {
+                 oamd_selfplay_config c{temperature_moves, temperature, 0, 0};
+                 int32_t plies = 0;
+                 check(oamd_arena_play(a.h, reinterpret_cast<oamd_net*>(net_a), b.h, reinterpret_cast<oamd_net*>(net_b),
+                                       &c, max_plies, reinterpret_cast<int32_t*>(actions),
+                                       reinterpret_cast<int32_t*>(finished), reinterpret_cast<int32_t*>(discs), &plies));
+                 return plies;
+             })
         .def("enable_timing", [](Engine& e, int every) { check(oamd_engine_enable_timing(e.h, every)); },
              py::arg("every") = 1)
         .def("set_pipeline", [](Engine& e, int groups) { check(oamd_engine_set_pipeline(e.h, groups)); })

@@ -1012,6 +1012,7 @@ __device__ void init_game(const EngineView& E, int g, uint64_t seed) {
     gs->key = mix64(seed ^ mix64((uint64_t)g + 0x632BE59BD9B4E019ULL));
     gs->event = 0;
     gs->ply = 0;
+    gs->arena = 0;
     for (int k = 0; k < 16; ++k) gs->hist[k] = -1;
 }
 
@@ -1218,6 +1219,59 @@ __global__ void k_random_openings(EngineView E, int max_moves, uint64_t seed) {
 
 constexpr int kFinNoTargets = 4, kFinOverflow = 8;
 
+// The move a game plays from its searched root (one wave; train.py:421-430,
+// player.py:250-256): temperature sampling while the game's ply <
+// temperature_moves, else argmax of the root visits with a uniform random
+// tie-break; uniform over the legal actions when the root is unexpanded. One
+// draw from the game's stream at its current event (the caller advances it).
+// Shared by the self-play driver and the arena.
+__device__ __forceinline__ int choose_root_action(const EngineView& E, const GameState* gs, size_t base,
+                                                  const NodeLink& lk, const NodePos& rp, int temperature_moves,
+                                                  float temperature) {
+    const int lane = lane_id();
+    const int nc = lk.n_children;
+    const int na = rp.legal ? popcount64(rp.legal) : 1;
+    int n = 0;
+    if (lane < nc) n = E.stat[base + lk.first_child + lane].n;
+    const uint64_t ev = gs->event;
+    const float u = uniform(stream_key(gs->key, ev, 0), 0);
+    int j = 0;
+    if (nc == 0) {
+        j = (int)(u * (float)na);  // unexpanded root: uniform over legal actions
+        if (j >= na) j = na - 1;
+    } else if (gs->ply < temperature_moves) {
+        // p ~ N^(1/temperature) (train.py:423-426); cdf search like numpy.random.choice
+        const float w = lane < nc ? powf((float)n, 1.0f / temperature) : 0.0f;
+        float sum = 0.0f;
+        float cdf = 0.0f;
+        for (int k = 0; k < nc; ++k) {
+            sum += readlane_f(w, k);
+            if (k == lane) cdf = sum;
+        }
+        if (sum > 0.0f) {
+            const float target = u * sum;
+            const bool above = lane < nc && cdf > target;
+            const uint64_t b = __ballot(above);
+            j = b ? __ffsll((unsigned long long)b) - 1 : nc - 1;
+        } else {
+            j = (int)(u * (float)nc);
+            if (j >= nc) j = nc - 1;
+        }
+    } else {
+        // argmax with uniform random tie-break (train.py:428-430)
+        int m = n;
+        m = wave_max_i(m);
+        const uint64_t ties = __ballot(lane < nc && n == m);
+        const int nt = popcount64(ties);
+        int k = (int)(u * (float)nt);
+        if (k >= nt) k = nt - 1;
+        uint64_t rem = ties;
+        for (int x = 0; x < k; ++x) rem &= rem - 1;
+        j = __ffsll((unsigned long long)rem) - 1;
+    }
+    return action_of_child(rp.legal, j);
+}
+
 // One self-play move of game g (one wave): outputs at index g of the given
 // per-move slices.
 __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const SelfplayParams& sp, int g,
@@ -1237,46 +1291,8 @@ __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const Se
                        (gs->flags & kOverflow ? kFinOverflow : 0);
     int action = -1;
     if (lk.player != 0) {
-        const int na = rp.legal ? popcount64(rp.legal) : 1;
-        int n = 0;
-        if (lane < nc) n = E.stat[base + lk.first_child + lane].n;
         const uint64_t ev = gs->event;
-        const float u = uniform(stream_key(gs->key, ev, 0), 0);
-        int j = 0;
-        if (nc == 0) {
-            j = (int)(u * (float)na);  // unexpanded root: uniform over legal actions
-            if (j >= na) j = na - 1;
-        } else if (gs->ply < sp.temperature_moves) {
-            // p ~ N^(1/temperature) (train.py:423-426); cdf search like numpy.random.choice
-            const float w = lane < nc ? powf((float)n, 1.0f / sp.temperature) : 0.0f;
-            float sum = 0.0f;
-            float cdf = 0.0f;
-            for (int k = 0; k < nc; ++k) {
-                sum += readlane_f(w, k);
-                if (k == lane) cdf = sum;
-            }
-            if (sum > 0.0f) {
-                const float target = u * sum;
-                const bool above = lane < nc && cdf > target;
-                const uint64_t b = __ballot(above);
-                j = b ? __ffsll((unsigned long long)b) - 1 : nc - 1;
-            } else {
-                j = (int)(u * (float)nc);
-                if (j >= nc) j = nc - 1;
-            }
-        } else {
-            // argmax with uniform random tie-break (train.py:428-430)
-            int m = n;
-            m = wave_max_i(m);
-            const uint64_t ties = __ballot(lane < nc && n == m);
-            const int nt = popcount64(ties);
-            int k = (int)(u * (float)nt);
-            if (k >= nt) k = nt - 1;
-            uint64_t rem = ties;
-            for (int x = 0; x < k; ++x) rem &= rem - 1;
-            j = __ffsll((unsigned long long)rem) - 1;
-        }
-        action = action_of_child(rp.legal, j);
+        action = choose_root_action(E, gs, base, lk, rp, sp.temperature_moves, sp.temperature);
         if (sp.emit_targets && feat_out && nc > 0) {
             const int C = 1 + 2 * E.H;
             for (int t = 0; t < 8; ++t)
@@ -1321,6 +1337,139 @@ __global__ __launch_bounds__(64) void k_selfplay_move(EngineView E, SelfplayPara
         return;
     }
     selfplay_move_game(E, sp, g, actions, finished, feat_out, pol_out);
+}
+
+// Per-game search mask (oamd_engine_set_active): k_tree, k_selfplay_move and
+// k_apply_actions leave inactive games alone. active == nullptr: every game.
+__global__ void k_set_active(EngineView E, const uint8_t* active) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    GameState* gs = E.games + g;
+    const bool on = !active || active[g] != 0;
+    gs->flags = (gs->flags & ~(int)kActive) | (on ? (int)kActive : 0);
+}
+
+// ---------------------------------------------------------------------------
+// Arena: match g is game g of two engines, one tree per player as the
+// reference's two AlphaZeroPlayers each own an MCTS (player.py:177-259). Per
+// ply only the side to move searches (its tree alone carries kActive), the
+// chosen action moves both roots (play_game, player.py:74-76), so each side
+// keeps its subtree across its own and the opponent's moves.
+// ---------------------------------------------------------------------------
+// whether engine A's net moves at a position whose side to move is `player`
+__device__ __forceinline__ bool arena_a_moves(int arena, int player) { return (player == 1) == (arena == 1); }
+
+__device__ __forceinline__ void arena_set_mover(GameState* ga, GameState* gb, int player) {
+    const int fa = ga->flags & ~(int)kActive, fb = gb->flags & ~(int)kActive;
+    const bool running = player != 0;
+    const bool a = arena_a_moves(ga->arena, player);
+    ga->flags = fa | (running && a ? (int)kActive : 0);
+    gb->flags = fb | (running && !a ? (int)kActive : 0);
+}
+
+// Reset both games of every match, play the opening plies (openings: (G,
+// plies) actions, -1 = none) in both trees, and leave kActive in the tree of
+// the side to move only. An illegal ply ends the match's opening there.
+__global__ void k_arena_begin(EngineView EA, EngineView EB, uint64_t seed_a, uint64_t seed_b, const int32_t* openings,
+                              int plies, const uint8_t* a_is_white) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= EA.G) return;
+    init_game(EA, g, seed_a);
+    init_game(EB, g, seed_b);
+    GameState* ga = EA.games + g;
+    GameState* gb = EB.games + g;
+    const size_t base = (size_t)g * EA.cap;
+    for (int k = 0; openings && k < plies; ++k) {
+        const int a = openings[(size_t)g * plies + k];
+        const int root = ga->root;
+        const int player = load_link(EA.link + base + root).player;
+        const uint64_t legal = EA.pos[base + root].legal;
+        const bool ok = player != 0 && (a == 64 ? legal == 0 : (a >= 0 && a < 64 && ((legal >> (63 - a)) & 1ULL)));
+        if (!ok) break;
+        move_root(EA, g, a);
+        move_root(EB, g, a);
+    }
+    ga->ply = 0;
+    gb->ply = 0;
+    ga->arena = gb->arena = a_is_white && a_is_white[g] ? 2 : 1;
+    arena_set_mover(ga, gb, load_link(EA.link + base + ga->root).player);
+}
+
+// *remaining = matches still running (both roots of an arena match not terminal)
+__global__ void k_arena_count(EngineView EA, int32_t* remaining) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= EA.G) return;
+    const GameState* ga = EA.games + g;
+    if (ga->arena != 0 && load_link(EA.link + (size_t)g * EA.cap + ga->root).player != 0 &&
+        (ga->arena & kArenaDesync) == 0)
+        atomicAdd(remaining, 1);
+}
+
+// One ply of match g (one wave). finished[g] is updated, never cleared: bits
+// 0-1 the outcome once the match ends (1 draw, 2 black won, 3 white won, as
+// k_selfplay_move reports it), bit 2 a move from an unexpanded root (uniform),
+// bit 3 a node pool overflowed, bit 4 the two trees' roots differ (the match
+// stops). actions[g] = the action played, -1 when the match is over.
+__global__ __launch_bounds__(64) void k_arena_move(EngineView EA, EngineView EB, SelfplayParams sp, int32_t* actions,
+                                                   int32_t* finished, int32_t* discs, int32_t* remaining) {
+    const int g = (int)blockIdx.x;
+    const int lane = lane_id();
+    GameState* ga = EA.games + g;
+    GameState* gb = EB.games + g;
+    const size_t base_a = (size_t)g * EA.cap, base_b = (size_t)g * EB.cap;
+    const int arena = ga->arena;
+    const NodeLink la = load_link(EA.link + base_a + ga->root);
+    const NodeLink lb = load_link(EB.link + base_b + gb->root);
+    const NodePos pa = EA.pos[base_a + ga->root];
+    const NodePos pb = EB.pos[base_b + gb->root];
+    int action = -1;
+    if ((arena & 3) == 0 || (arena & kArenaDesync) || la.player == 0) {
+        if (lane == 0 && actions) actions[g] = -1;
+        return;
+    }
+    if (la.player != lb.player || pa.p1 != pb.p1 || pa.p2 != pb.p2) {
+        if (lane == 0) {
+            ga->arena = gb->arena = arena | kArenaDesync;
+            arena_set_mover(ga, gb, 0);
+            if (actions) actions[g] = -1;
+            if (finished) finished[g] |= kArenaDesync;
+            if (remaining) atomicSub(remaining, 1);
+        }
+        return;
+    }
+    const bool a_moves = arena_a_moves(arena, la.player);
+    GameState* gm = a_moves ? ga : gb;
+    const int nc = a_moves ? la.n_children : lb.n_children;
+    int status = (nc == 0 ? kFinNoTargets : 0) | ((ga->flags | gb->flags) & kOverflow ? kFinOverflow : 0);
+    const uint64_t ev = gm->event;
+    if (a_moves) action = choose_root_action(EA, ga, base_a, la, pa, sp.temperature_moves, sp.temperature);
+    else action = choose_root_action(EB, gb, base_b, lb, pb, sp.temperature_moves, sp.temperature);
+    if (lane == 0) {
+        gm->event = ev + 1;  // the side that does not move draws nothing
+        move_root(EA, g, action);
+        move_root(EB, g, action);
+    }
+    __builtin_amdgcn_wave_barrier();
+    wait_stores();
+    if (lane == 0) {
+        const int r2 = ga->root;
+        const NodeLink l2 = load_link(EA.link + base_a + r2);
+        status |= (ga->flags | gb->flags) & kOverflow ? kFinOverflow : 0;
+        int fin = 0;
+        if (l2.player == 0) {
+            const NodePos p2 = EA.pos[base_a + r2];
+            const int b = popcount64(p2.p1), w = popcount64(p2.p2);
+            fin = b > w ? 2 : (b < w ? 3 : 1);
+            if (discs) {
+                discs[2 * g] = b;
+                discs[2 * g + 1] = w;
+            }
+            if (remaining) atomicSub(remaining, 1);
+        }
+        arena_set_mover(ga, gb, l2.player);
+        if (actions) actions[g] = action;
+        if (finished && (fin | status)) finished[g] |= fin | status;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1504,6 +1653,23 @@ void launch_selfplay_move(const EngineView& E, const SelfplayParams& sp, int g0,
                           int32_t* finished, float* feat, float* pol, hipStream_t s) {
     if (ng > 0)
         hipLaunchKernelGGL(k_selfplay_move, dim3(ng), dim3(64), 0, s, E, sp, g0, actions, finished, feat, pol);
+}
+void launch_set_active(const EngineView& E, const uint8_t* active, hipStream_t s) {
+    hipLaunchKernelGGL(k_set_active, dim3(blocks_for(E.G, 64)), dim3(64), 0, s, E, active);
+}
+void launch_arena_begin(const EngineView& EA, const EngineView& EB, uint64_t seed_a, uint64_t seed_b,
+                        const int32_t* openings, int plies, const uint8_t* a_is_white, hipStream_t s) {
+    if (EA.G != EB.G) return;  // caller validated
+    hipLaunchKernelGGL(k_arena_begin, dim3(blocks_for(EA.G, 64)), dim3(64), 0, s, EA, EB, seed_a, seed_b, openings,
+                       plies, a_is_white);
+}
+void launch_arena_count(const EngineView& EA, int32_t* remaining, hipStream_t s) {
+    hipLaunchKernelGGL(k_arena_count, dim3(blocks_for(EA.G, 64)), dim3(64), 0, s, EA, remaining);
+}
+void launch_arena_move(const EngineView& EA, const EngineView& EB, const SelfplayParams& sp, int32_t* actions,
+                       int32_t* finished, int32_t* discs, int32_t* remaining, hipStream_t s) {
+    if (EA.G != EB.G || EA.G <= 0) return;  // caller validated
+    hipLaunchKernelGGL(k_arena_move, dim3(EA.G), dim3(64), 0, s, EA, EB, sp, actions, finished, discs, remaining);
 }
 void launch_free_begin(const EngineView& E, int g0, int ng, int n_moves, int32_t* remaining, int32_t* actions,
                        int32_t* finished, int per_move, hipStream_t s) {

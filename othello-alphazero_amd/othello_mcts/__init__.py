@@ -4,6 +4,7 @@ Same import surface as cpp/src/othello_mcts/__init__.py:1-6 (``MCTS``,
 ``Position``, ``get_flips``, ``get_legal_moves``), backed by hand-written HIP
 kernels for gfx950 behind the C ABI in include/othello_mcts_amd.h. Additive
 API: ``BatchedMCTS`` (G games per GPU, on-device self-play driver),
+``Arena`` (G head-to-head matches between two nets, one tree per player),
 ``NativeNet`` (fused bf16/fp16 AlphaZeroNet forward, also from a reference
 checkpoint directory via ``load_checkpoint``), ``SelfPlayCollector`` /
 ``self_play`` (training samples in the reference's ``_self_play`` format) and
@@ -29,6 +30,7 @@ from ._othello_mcts_impl import (  # noqa: F401
     get_legal_moves,
 )
 from .batched import BatchedMCTS  # noqa: E402,F401
+from .arena import Arena, ArenaResult, paired_openings  # noqa: E402,F401
 from .native import NativeNet, load_checkpoint  # noqa: E402,F401
 from .selfplay import SelfPlayCollector, self_play  # noqa: E402,F401
 from .training import SampleBuffer, alphazero_loss, refresh_native, train_epoch  # noqa: E402,F401
@@ -48,4 +50,7 @@ __all__ = [
     "alphazero_loss",
     "train_epoch",
     "refresh_native",
+    "Arena",
+    "ArenaResult",
+    "paired_openings",
 ]

@@ -119,6 +119,19 @@ class BatchedMCTS:
         self._stream()
         self.engine.reset(game, seed)
 
+    def set_active(self, active=None) -> None:
+        """Per-game mask (G bools; None = every game): inactive games are left
+        alone by search, selfplay_move and apply_actions. reset() reactivates
+        the games it resets."""
+        self._stream()
+        if active is None:
+            self.engine.set_active(0)
+            return
+        m = torch.as_tensor(active).to(self.device).ne(0).to(torch.uint8).contiguous()
+        if m.shape != (self.num_games,):
+            raise ValueError(f"Expected {self.num_games} mask entries, but got shape {tuple(m.shape)}.")
+        self.engine.set_active(m.data_ptr())
+
     def random_openings(self, max_moves: int = 8, seed: int = 0) -> None:
         self._stream()
         self.engine.random_openings(max_moves, seed)
