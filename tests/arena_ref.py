@@ -108,16 +108,19 @@ def play_match(key_a: int, key_b: int, opening, a_is_white: bool, temperature_mo
 _CACHE: dict = {}
 
 
-def reference_matches(temperature_moves: int = 0) -> list[dict]:
+def reference_matches(temperature_moves: int = 0, eval_a=stub_a, eval_b=stub_b) -> list[dict]:
     """The MATCHES reference matches of the tests' setup (computed once per
-    session): keys of engines seeded 0 (A) and 1 (B), pair openings, odd matches
-    swapped, A = equivariant_stub, B = stub_b."""
-    if temperature_moves not in _CACHE:
+    session and pair of evaluators): keys of engines seeded 0 (A) and 1 (B),
+    pair openings, odd matches swapped, by default A = equivariant_stub,
+    B = stub_b."""
+    k = (temperature_moves, eval_a, eval_b)
+    if k not in _CACHE:
         ops, sw = openings(), swapped()
-        _CACHE[temperature_moves] = [
-            play_match(game_key(0, g), game_key(1, g), ops[g], bool(sw[g]), temperature_moves)
+        _CACHE[k] = [
+            play_match(game_key(0, g), game_key(1, g), ops[g], bool(sw[g]), temperature_moves,
+                       eval_a=eval_a, eval_b=eval_b)
             for g in range(MATCHES)]
-    return _CACHE[temperature_moves]
+    return _CACHE[k]
 
 
 def summary(match: dict) -> tuple[int, int, int, int, int]:

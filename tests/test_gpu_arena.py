@@ -35,10 +35,24 @@ def test_arena_matches_equal_the_reference_ply_by_ply(temperature_moves):
     the other tree was not touched by the ply's search (the mask); after it
     both roots are the oracle's position; actions, lengths, results and discs
     are the reference's."""
+    _matches_equal_the_reference(temperature_moves, R.reference_matches(temperature_moves), STUB_A, STUB_B)
+
+
+def test_arena_matches_equal_the_reference_with_asymmetric_evaluators():
+    """The same, with two evaluators that see the per-leaf board symmetry
+    (tests/asym_stub.py; both default stubs are equivariant, so a wrong draw or
+    un-transform in either engine's stream is invisible above)."""
+    import asym_stub as A
+
+    ref = R.reference_matches(0, A.asymmetric_stub_a, A.asymmetric_stub_b)
+    assert ref != R.reference_matches(0)
+    _matches_equal_the_reference(0, ref, _t(A.asymmetric_stub_a), _t(A.asymmetric_stub_b))
+
+
+def _matches_equal_the_reference(temperature_moves, ref, STUB_A, STUB_B):
     import othello_mcts as om
 
     G = R.MATCHES
-    ref = R.reference_matches(temperature_moves)
     arena = om.Arena.create(G, seed=0, node_capacity=1 << 16, **{k: v for k, v in R.SETUP.items()
                                                                   if k != "dirichlet_epsilon"})
     assert arena.a.config.dirichlet_epsilon == 0.0 and arena.b.config.dirichlet_epsilon == 0.0
