@@ -340,6 +340,69 @@ int oamd_arena_play(oamd_engine *a, oamd_net *net_a, oamd_engine *b, oamd_net *n
                     const oamd_selfplay_config *cfg, int32_t max_plies, int32_t *actions_dev,
                     int32_t *finished_dev, int32_t *discs_dev, int32_t *plies_host);
 
+/* ------------------------------------------------------------------------ */
+/* Packed replay buffer: a ring of POSITIONS (2H bitboards, the side to move, */
+/* one 65-entry policy, one value: 16H + 265 bytes) instead of 8 fp32 samples */
+/* per position; the 8 board symmetries are produced when a minibatch is      */
+/* gathered. Replaces the sample lists of train.py:432-452 (_self_play's      */
+/* value assignment) and the per-minibatch indexing of train.py:487-489.      */
+/* The caller owns every buffer (the Python layer keeps them as torch         */
+/* tensors); the struct below only points at them.                            */
+/* ------------------------------------------------------------------------ */
+
+/* sticky bits of counters[3]: rows the add / gather kernels refused */
+#define OAMD_REPLAY_OVERFLOW 1   /* finished bit 3: the game's node pool overflowed */
+#define OAMD_REPLAY_NO_TARGETS 2 /* finished bit 2 on a played game: no targets were written */
+#define OAMD_REPLAY_TOO_LONG 4   /* a game staged more than max_moves moves */
+#define OAMD_REPLAY_BAD_ID 8     /* a gather id outside [0, 8 * size) */
+
+typedef struct oamd_replay_view {
+    int32_t device;       /* HIP device of every pointer below */
+    int32_t num_games;    /* G >= 1 */
+    int32_t history_size; /* H in [1, 15] */
+    int32_t max_moves;    /* staged moves per game, >= 1; G * max_moves < 2^31 */
+    int64_t capacity;     /* ring length in positions, >= 1 */
+    /* ring, structure of arrays */
+    uint64_t *boards; /* (capacity, 2H): planes 1..2H of the untransformed sample, square i = bit 63 - i */
+    float *policy;    /* (capacity, 65): the transform-0 policy */
+    float *value;     /* (capacity) */
+    uint8_t *player;  /* (capacity): plane 0 (0 black to move, 1 white) */
+    /* staging: the moves of the games still running */
+    uint64_t *stage_boards; /* (G, max_moves, 2H) */
+    float *stage_policy;    /* (G, max_moves, 65) */
+    uint8_t *stage_player;  /* (G, max_moves) */
+    int32_t *moves;         /* (G) staged moves per game */
+    int32_t *pending;       /* (G) scratch of the add call */
+    /* [0] head (next slot written), [1] size (live positions), [2] games
+     * completed, [3] sticky OAMD_REPLAY_* bits; zero-initialised by the caller */
+    int64_t *counters;
+} oamd_replay_view;
+
+/* One or n_moves moves of every game, as oamd_engine_selfplay_move /
+ * oamd_engine_selfplay_steps (emit_targets = 1) wrote them: actions_dev (G),
+ * finished_dev (G), features_dev (G, 8, 1+2H, 8, 8), policy_dev (G, 8, 65);
+ * n_moves > 1: the stacked per_move_outputs = 1 layout, slices handled in
+ * order. Only the transform-0 slice is read. Per move: every game with
+ * actions >= 0 stages one record; then the games whose finished bits 0-1 are
+ * set move to the ring in ascending game order with their value targets (the
+ * outcome for black, negated where white was to move), oldest positions
+ * overwritten. A row with finished bit 3, with bit 2 on a played game, or of
+ * a game already holding max_moves moves sets its sticky bit instead and is
+ * skipped (a game that finished in such a row is dropped). Enqueued only. */
+int oamd_replay_add(const oamd_replay_view *view, int32_t n_moves, const int32_t *actions_dev,
+                    const int32_t *finished_dev, const float *features_dev, const float *policy_dev,
+                    void *stream);
+/* ids_dev (n) int64: id s = position s >> 3 (counted from the oldest live
+ * position) under board transform s & 7 (transformation.h:40-57). Outputs:
+ * features_dev (n, 1+2H, 8, 8), policy_dev (n, 65), value_dev (n) fp32. An id
+ * outside [0, 8 * size) gives a zero row and sets OAMD_REPLAY_BAD_ID.
+ * Enqueued only. */
+int oamd_replay_gather(const oamd_replay_view *view, const int64_t *ids_dev, int64_t n, float *features_dev,
+                       float *policy_dev, float *value_dev, void *stream);
+/* Host outputs (each may be NULL); waits for the stream. */
+int oamd_replay_counters(const oamd_replay_view *view, int64_t *size, int64_t *head, int64_t *games_completed,
+                         int32_t *flags, void *stream);
+
 /* Timing accumulated over the timed oamd_engine_search calls (HIP events on
  * the launching streams; a query waits for the searches still in flight):
  * total ms spent in the NN kernel, number of NN launches, rows launched

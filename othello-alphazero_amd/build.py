@@ -1,6 +1,6 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
-  liboamd.so               HIP kernels (tree.hip, resnet.hip) + the C ABI (capi.hip),
+  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip) + the C ABI (capi.hip),
                            hipcc --offload-arch=gfx950
   _othello_mcts_impl*.so   pybind11 host layer (pybind_module.cpp) over the C ABI
 
@@ -39,6 +39,8 @@ NO_SCALAR_LOADS = ["-mllvm", "-amdgpu-scalarize-global-loads=false"]
 UNITS = {
     "tree.hip": EXACT + NO_SCALAR_LOADS,
     "capi.hip": EXACT,
+    # packed replay buffer: its value targets are SampleBuffer's, bit for bit
+    "replay.hip": EXACT,
     # accumulators and fragments in arch VGPRs: the default heuristic parks the
     # 128 accumulators of a 1-wave/SIMD tile in AGPRs and shuffles them per MFMA;
     # the max-ILP machine scheduler: k_resnet_w8 0.895-0.900 vs 0.907-0.913 ms per

@@ -20,6 +20,7 @@
 
 #include "engine.h"
 #include "kernels.h"
+#include "replay.h"
 #include "timing.h"
 
 using namespace oamd;
@@ -2007,6 +2008,81 @@ int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* n
         }
     }
     if (plies_host) *plies_host = ply;
+    return OAMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Packed replay buffer (replay.hip): the caller owns the storage
+// ---------------------------------------------------------------------------
+static int replay_checks(const oamd_replay_view* v) {
+    if (!v) return fail(OAMD_INVALID_ARGUMENT, "replay: view is NULL");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess) n_dev = 0;
+    if (v->device < 0 || v->device >= n_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: no HIP device " + std::to_string(v->device));
+    if (v->num_games < 1)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected num_games >= 1, but got " + std::to_string(v->num_games) + ".");
+    if (v->history_size < 1 || v->history_size > 15)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "Expected 1 <= history_size <= 15, but got " + std::to_string(v->history_size) + ".");
+    if (v->max_moves < 1)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected max_moves >= 1, but got " + std::to_string(v->max_moves) + ".");
+    if ((int64_t)v->num_games * v->max_moves > INT32_MAX)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: num_games * max_moves must be below 2^31");
+    if (v->capacity < 1)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected capacity >= 1, but got " + std::to_string(v->capacity) + ".");
+    if (!v->boards || !v->policy || !v->value || !v->player || !v->stage_boards || !v->stage_policy ||
+        !v->stage_player || !v->moves || !v->pending || !v->counters)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: every buffer of the view is required");
+    return OAMD_OK;
+}
+
+int oamd_replay_add(const oamd_replay_view* view, int32_t n_moves, const int32_t* actions_dev,
+                    const int32_t* finished_dev, const float* features_dev, const float* policy_dev, void* stream) {
+    if (int rc = replay_checks(view)) return rc;
+    if (n_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "replay: n_moves must be >= 0");
+    if (n_moves == 0) return OAMD_OK;
+    if (!actions_dev || !finished_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: actions and finished buffers are required");
+    if (!features_dev || !policy_dev)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "replay: features and policy buffers are required (self-play moves with emit_targets = 1)");
+    DeviceGuard dg(view->device);
+    const size_t G = (size_t)view->num_games;
+    const size_t C = 1 + 2 * (size_t)view->history_size;
+    for (int32_t i = 0; i < n_moves; ++i) {
+        launch_replay_add(*view, actions_dev + i * G, finished_dev + i * G, features_dev + i * G * 8 * C * 64,
+                          policy_dev + i * G * 8 * 65, (hipStream_t)stream);
+        LAUNCHCHK();
+    }
+    return OAMD_OK;
+}
+
+int oamd_replay_gather(const oamd_replay_view* view, const int64_t* ids_dev, int64_t n, float* features_dev,
+                       float* policy_dev, float* value_dev, void* stream) {
+    if (int rc = replay_checks(view)) return rc;
+    if (n < 0 || n > INT32_MAX) return fail(OAMD_INVALID_ARGUMENT, "replay: n must be in [0, 2^31)");
+    if (n == 0) return OAMD_OK;
+    if (!ids_dev) return fail(OAMD_INVALID_ARGUMENT, "replay: ids buffer is required");
+    if (!features_dev || !policy_dev || !value_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: features, policy and value output buffers are required");
+    DeviceGuard dg(view->device);
+    launch_replay_gather(*view, ids_dev, n, features_dev, policy_dev, value_dev, (hipStream_t)stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+int oamd_replay_counters(const oamd_replay_view* view, int64_t* size, int64_t* head, int64_t* games_completed,
+                         int32_t* flags, void* stream) {
+    if (int rc = replay_checks(view)) return rc;
+    DeviceGuard dg(view->device);
+    int64_t c[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(c, view->counters, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (head) *head = c[kReplayHead];
+    if (size) *size = c[kReplaySize];
+    if (games_completed) *games_completed = c[kReplayGames];
+    if (flags) *flags = (int32_t)c[kReplayFlags];
     return OAMD_OK;
 }
 

@@ -753,6 +753,44 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
             return py::make_tuple(lv, sc, ex, cr, la);
         });
 
+    // ---- packed replay buffer (othello_mcts/replay.py): the tensors' data_ptr ints ----
+    py::class_<oamd_replay_view>(m, "_ReplayView")
+        .def(py::init([](int device, int num_games, int history_size, int max_moves, int64_t capacity,
+                         uintptr_t boards, uintptr_t policy, uintptr_t value, uintptr_t player,
+                         uintptr_t stage_boards, uintptr_t stage_policy, uintptr_t stage_player, uintptr_t moves,
+                         uintptr_t pending, uintptr_t counters) {
+                 return oamd_replay_view{device, num_games, history_size, max_moves, capacity,
+                                         reinterpret_cast<uint64_t*>(boards), reinterpret_cast<float*>(policy),
+                                         reinterpret_cast<float*>(value), reinterpret_cast<uint8_t*>(player),
+                                         reinterpret_cast<uint64_t*>(stage_boards),
+                                         reinterpret_cast<float*>(stage_policy),
+                                         reinterpret_cast<uint8_t*>(stage_player), reinterpret_cast<int32_t*>(moves),
+                                         reinterpret_cast<int32_t*>(pending), reinterpret_cast<int64_t*>(counters)};
+             }),
+             "device"_a, "num_games"_a, "history_size"_a, "max_moves"_a, "capacity"_a, "boards"_a, "policy"_a,
+             "value"_a, "player"_a, "stage_boards"_a, "stage_policy"_a, "stage_player"_a, "moves"_a, "pending"_a,
+             "counters"_a)
+        .def("add",
+             [](const oamd_replay_view& v, int n_moves, uintptr_t actions, uintptr_t finished, uintptr_t feat,
+                uintptr_t pol, uintptr_t stream) {
+                 check(oamd_replay_add(&v, n_moves, reinterpret_cast<const int32_t*>(actions),
+                                       reinterpret_cast<const int32_t*>(finished), reinterpret_cast<const float*>(feat),
+                                       reinterpret_cast<const float*>(pol), reinterpret_cast<void*>(stream)));
+             })
+        .def("gather",
+             [](const oamd_replay_view& v, uintptr_t ids, int64_t n, uintptr_t feat, uintptr_t pol, uintptr_t val,
+                uintptr_t stream) {
+                 check(oamd_replay_gather(&v, reinterpret_cast<const int64_t*>(ids), n, reinterpret_cast<float*>(feat),
+                                          reinterpret_cast<float*>(pol), reinterpret_cast<float*>(val),
+                                          reinterpret_cast<void*>(stream)));
+             })
+        .def("counters", [](const oamd_replay_view& v, uintptr_t stream) {
+            int64_t size = 0, head = 0, games = 0;
+            int32_t flags = 0;
+            check(oamd_replay_counters(&v, &size, &head, &games, &flags, reinterpret_cast<void*>(stream)));
+            return py::make_tuple(size, head, games, flags);
+        });
+
     // GPU bitboard kernels over device buffers (data_ptr ints) for parity tests
     m.def("_gpu_legal_moves", [](uintptr_t me, uintptr_t opp, uintptr_t out, int64_t n, uintptr_t stream) {
         check(oamd_get_legal_moves((const uint64_t*)me, (const uint64_t*)opp, (uint64_t*)out, n, (void*)stream));

@@ -10,7 +10,9 @@ checkpoint directory via ``load_checkpoint``), ``SelfPlayCollector`` /
 ``self_play`` (training samples in the reference's ``_self_play`` format) and
 the training step beside the engine (``SampleBuffer``, ``train_epoch``,
 ``alphazero_loss``, ``refresh_native``: train.py:455-521 with the samples kept
-in HBM).
+in HBM) and ``ReplayBuffer`` / ``train_epoch_replay``: the same samples kept as
+packed positions (bitboards, 94 times smaller at H = 8) and expanded to the 8
+board symmetries when a minibatch is gathered.
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -33,7 +35,14 @@ from .batched import BatchedMCTS  # noqa: E402,F401
 from .arena import Arena, ArenaResult, paired_openings  # noqa: E402,F401
 from .native import NativeNet, load_checkpoint  # noqa: E402,F401
 from .selfplay import SelfPlayCollector, self_play  # noqa: E402,F401
-from .training import SampleBuffer, alphazero_loss, refresh_native, train_epoch  # noqa: E402,F401
+from .replay import ReplayBuffer  # noqa: E402,F401
+from .training import (  # noqa: E402,F401
+    SampleBuffer,
+    alphazero_loss,
+    refresh_native,
+    train_epoch,
+    train_epoch_replay,
+)
 
 __all__ = [
     "MCTS",
@@ -49,7 +58,9 @@ __all__ = [
     "SampleBuffer",
     "alphazero_loss",
     "train_epoch",
+    "train_epoch_replay",
     "refresh_native",
+    "ReplayBuffer",
     "Arena",
     "ArenaResult",
     "paired_openings",

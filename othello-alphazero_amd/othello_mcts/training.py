@@ -14,6 +14,8 @@ tensors, train.py:432-434) and back to the device per minibatch
 * ``train_epoch`` is ``_train``'s loop: shuffled minibatches, ``drop_last``,
   the same loss (``alphazero_loss``, train.py:494-499) and the same returned
   dict of running mean losses (train.py:513-518);
+* ``train_epoch_replay`` is the same loop over a packed ``ReplayBuffer``
+  (replay.py): the minibatches are expanded from bitboards by a gather kernel;
 * ``refresh_native`` pushes the updated weights into the ``NativeNet`` the
   engine searches with (one 5.4 MB upload for 128x10b).
 """
@@ -140,6 +142,35 @@ def train_epoch(neural_net: torch.nn.Module, optimizer: torch.optim.Optimizer, f
     return means
 
 
+def train_epoch_replay(neural_net: torch.nn.Module, optimizer: torch.optim.Optimizer, buf, batch_size: int,
+                       l2_weight: float = 1e-4, generator: torch.Generator | None = None) -> dict[str, float]:
+    """``train_epoch`` over a packed ``ReplayBuffer``: the same permutation of
+    the ``8 * size`` sample ids (``torch.randperm`` on the CPU with the same
+    generator), the same ``drop_last`` batches in the same order, the same loss
+    and the same returned running means. Each batch is expanded from the packed
+    positions by ``buf.gather`` instead of indexed out of fp32 sample arrays,
+    so with equal contents the two loops feed the net identical tensors."""
+    neural_net.train()
+    dev = next(neural_net.parameters()).device
+    n = 8 * buf.size
+    perm = torch.randperm(n, generator=generator, device="cpu").to(buf.device)
+    sums = {"total_loss": 0.0, "policy_loss": 0.0, "value_loss": 0.0, "l2_loss": 0.0}
+    count = 0
+    means: dict[str, float] = {}
+    for b in range(n // batch_size):
+        x, tp, tv = (t.to(dev, torch.float32) for t in buf.gather(perm[b * batch_size:(b + 1) * batch_size]))
+        optimizer.zero_grad()
+        out = neural_net(x)
+        losses = alphazero_loss(out["policy"], out["value"], tp, tv, neural_net.parameters(), l2_weight)
+        losses["total_loss"].backward()
+        optimizer.step()
+        count += 1
+        for k in sums:
+            sums[k] += losses[k].item()
+        means = {k: sums[k] / count for k in sums}
+    return means
+
+
 def refresh_native(native_net, neural_net: torch.nn.Module) -> None:
     """Upload the trained weights into the NativeNet the engine searches with
     (BN folded again, eval statistics)."""
@@ -147,4 +178,4 @@ def refresh_native(native_net, neural_net: torch.nn.Module) -> None:
     native_net.load_state_dict(mod.state_dict())
 
 
-__all__ = ["alphazero_loss", "SampleBuffer", "train_epoch", "refresh_native"]
+__all__ = ["alphazero_loss", "SampleBuffer", "train_epoch", "train_epoch_replay", "refresh_native"]

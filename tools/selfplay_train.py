@@ -12,7 +12,12 @@ trained net's are (trees of a trained net concentrate and
 descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
-Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games]
+Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds] [packed]
+
+packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
+million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
+self-play phase; minibatches expanded by train_epoch_replay) instead of the
+fp32 SampleBuffer (400,000 samples in 1.85 GB, one add per move).
 """
 
 import json
@@ -77,6 +82,7 @@ def main():
     out = Path(sys.argv[1])
     iterations = int(sys.argv[2]) if len(sys.argv) > 2 else 40
     G = int(sys.argv[3]) if len(sys.argv) > 3 else 256
+    packed = "packed" in sys.argv[5:]
     moves_per_iter = 64
     torch.manual_seed(0)
     dev = torch.device("cuda", 0)
@@ -88,7 +94,10 @@ def main():
     b = om.BatchedMCTS(G, history_size=8, num_simulations=800, num_threads=2, batch_size=16,
                        dirichlet_epsilon=0.25, dirichlet_alpha=0.5, seed=77)
     b.reset()
-    buf = om.SampleBuffer(G, 17, capacity=400_000, device=dev)
+    if packed:
+        buf = om.ReplayBuffer(G, 8, capacity=500_000, device=dev)
+    else:
+        buf = om.SampleBuffer(G, 17, capacity=400_000, device=dev)
     log = []
     t_start = time.time()
     gen = torch.Generator().manual_seed(1)
@@ -98,13 +107,21 @@ def main():
         for _ in range(moves_per_iter // 16):  # 16 moves per call: bounded output buffers
             o = b.selfplay_steps(native, 16, temperature_moves=12, opening_moves=0, emit_targets=True,
                                  keep_all=True)
-            for i in range(16):
-                buf.add({k: v[i] for k, v in o.items()})
+            if packed:
+                buf.add(o)
+            else:
+                for i in range(16):
+                    buf.add({k: v[i] for k, v in o.items()})
         torch.cuda.synchronize()
         t1 = time.time()
-        n = buf.size
-        losses = om.train_epoch(model, opt, buf.features[:n], buf.policies[:n], buf.values[:n], 256,
-                                l2_weight=1e-4, generator=gen)
+        if packed:
+            buf.check()
+            n = 8 * buf.size
+            losses = om.train_epoch_replay(model, opt, buf, 256, l2_weight=1e-4, generator=gen)
+        else:
+            n = buf.size
+            losses = om.train_epoch(model, opt, buf.features[:n], buf.policies[:n], buf.values[:n], 256,
+                                    l2_weight=1e-4, generator=gen)
         model.eval()
         om.refresh_native(native, model)
         torch.cuda.synchronize()
@@ -119,7 +136,8 @@ def main():
     np.savez_compressed(str(out) + ".npz", **{k: (v.astype(np.float16) if v.dtype == np.float32 else v)
                                              for k, v in sd.items()})
     Path(str(out) + ".json").write_text(json.dumps({"iterations": log, "games_per_engine": G,
-                                                    "moves_per_iteration": moves_per_iter}, indent=1))
+                                                    "moves_per_iteration": moves_per_iter,
+                                                    "buffer": "packed" if packed else "fp32"}, indent=1))
 
 
 if __name__ == "__main__":
