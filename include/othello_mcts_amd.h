@@ -403,6 +403,44 @@ int oamd_replay_gather(const oamd_replay_view *view, const int64_t *ids_dev, int
 int oamd_replay_counters(const oamd_replay_view *view, int64_t *size, int64_t *head, int64_t *games_completed,
                          int32_t *flags, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Exact endgame solver: the last plies solved by brute force on bitboards.  */
+/* Stands in for the external engine behind the reference's EgaroucidPlayer  */
+/* (player.py:262-321) as a yardstick of correct play. The game ends when     */
+/* neither side can move; the result is the plain disc difference (mover      */
+/* minus opponent, no bonus for empties: play_game, player.py:83-92).         */
+/* move_scores[a], for every legal action a of the position (0..63, or 64     */
+/* when the mover must pass), is the exact result for the side to move after  */
+/* a and perfect play by both; every other entry is OAMD_SOLVE_NONE. score =  */
+/* the maximum, best_action = its first index. A position where neither side  */
+/* can move is terminal whatever `player` says: score = black minus white,    */
+/* best_action = -1. legal_moves / next_legal_moves are ignored.              */
+/* ------------------------------------------------------------------------ */
+#define OAMD_SOLVE_NONE (-128)
+/* per-position flags; a flagged position has score -128, best_action -1 */
+#define OAMD_SOLVE_TOO_MANY_EMPTIES 1 /* more than max_empties empties: not searched */
+#define OAMD_SOLVE_NODE_LIMIT 2       /* a root action visited more than node_limit positions */
+#define OAMD_SOLVE_INVALID 4          /* overlapping discs, player outside 0..2, or 0 while a side can move */
+
+/* bytes of the caller-owned workspace for n positions */
+int oamd_solve_workspace_bytes(int64_t n, int64_t *bytes);
+/* n positions on `device`; outputs (device, each may be NULL except move_scores):
+ * move_scores_dev (n, 65) int32, score_dev (n) int32, best_action_dev (n) int32,
+ * flags_dev (n) int32, nodes_dev (n) int64 (positions visited, summed over the
+ * root actions; the same count as the host solver's). max_empties in [0, 16];
+ * node_limit >= 1 is a budget per root action. workspace: caller-owned, size
+ * from oamd_solve_workspace_bytes(n). Enqueued only. */
+int oamd_solve_endgames(int32_t device, const oamd_position *pos_dev, int64_t n, int32_t max_empties,
+                        int64_t node_limit, int32_t *move_scores_dev, int32_t *score_dev,
+                        int32_t *best_action_dev, int32_t *flags_dev, int64_t *nodes_dev,
+                        void *workspace_dev, void *stream);
+/* The same solver on the host for one position (scalar form, like
+ * oamd_host_legal_moves; same source, csrc/solver.h). move_scores65 is
+ * required, the other outputs may be NULL. */
+int oamd_host_solve_endgame(const oamd_position *pos_host, int32_t max_empties, int64_t node_limit,
+                            int32_t *move_scores65, int32_t *score, int32_t *best_action,
+                            int32_t *flags, int64_t *nodes);
+
 /* Timing accumulated over the timed oamd_engine_search calls (HIP events on
  * the launching streams; a query waits for the searches still in flight):
  * total ms spent in the NN kernel, number of NN launches, rows launched

@@ -91,6 +91,15 @@ int oamd_engine_set_free_running(oamd_engine *e, int32_t enable);
 int oamd_engine_tree_work(oamd_engine *e, int64_t *levels, int64_t *children_scanned, int64_t *expansions,
                           int64_t *children_created, int64_t *launches);
 
+/* oamd_solve_endgames with an explicit number of 64-lane workgroups (>= 1)
+ * instead of the chip-filling default: one workgroup pushes every item through
+ * 64 lanes, each taking the next item when its own is done. Scores, flags and
+ * node counts do not depend on it. */
+int oamd_solve_endgames_grid(int32_t device, const oamd_position *pos_dev, int64_t n, int32_t max_empties,
+                             int64_t node_limit, int32_t *move_scores_dev, int32_t *score_dev,
+                             int32_t *best_action_dev, int32_t *flags_dev, int64_t *nodes_dev,
+                             void *workspace_dev, int32_t workgroups, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

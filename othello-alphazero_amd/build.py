@@ -1,6 +1,7 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
-  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip) + the C ABI (capi.hip),
+  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip) + the C ABI
+                           (capi.hip),
                            hipcc --offload-arch=gfx950
   _othello_mcts_impl*.so   pybind11 host layer (pybind_module.cpp) over the C ABI
 
@@ -48,6 +49,9 @@ UNITS = {
     "resnet.hip": os.environ.get("OAMD_RESNET_FLAGS",
                                  "-mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-sched-strategy=max-ilp").split()
     + ["-Rpass-analysis=kernel-resource-usage"],
+    # exact endgame solver: integer code; its searcher stacks are LDS, and the
+    # build fails if the solve kernel reports any scratch (check_solver_scratch)
+    "solver.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 
@@ -62,9 +66,37 @@ def run(cmd: list[str]) -> None:
         sys.stderr.write(" ".join(cmd) + "\n" + r.stdout + r.stderr)
         raise SystemExit(f"build failed: {cmd[-1]}")
     if "kernel-resource-usage" in " ".join(cmd):
-        check_w8_vgprs(r.stderr)
+        # the remarks of a unit are checked by that unit's rule only
+        unit = next((u for u in RESOURCE_CHECKS if str(CSRC / u) in cmd), None)
+        if unit:
+            RESOURCE_CHECKS[unit](r.stderr)
     elif r.stderr.strip():
         sys.stderr.write(r.stderr)
+
+
+def kernel_remarks(remarks: str):
+    """(kernel name, field, value) of -Rpass-analysis=kernel-resource-usage remarks."""
+    name = None
+    for ln in remarks.splitlines():
+        if "Function Name:" in ln:
+            name = ln.split("Function Name:")[1].split()[0]
+        elif name and "remark:" in ln and ":" in ln.split("remark:")[1]:
+            field, _, value = ln.split("remark:")[1].split("[-Rpass")[0].rpartition(":")
+            yield name, field.strip(), value.strip()
+
+
+def check_solver_scratch(remarks: str) -> None:
+    """solver.hip: k_solve's searcher stacks live in LDS; a runtime-indexed
+    per-thread array would land in scratch. Fail if k_solve reports any."""
+    seen = 0
+    for name, field, value in kernel_remarks(remarks):
+        if "k_solve" in name and "reduce" not in name and field.startswith("ScratchSize"):
+            seen += 1
+            if int(value.split()[0]) != 0:
+                raise SystemExit(f"build failed: {name} uses {value} bytes of scratch per lane: "
+                                 "the solver's stacks must stay in LDS")
+    if not seen:
+        raise SystemExit("build failed: no resource remark for k_solve in solver.hip")
 
 
 def check_w8_vgprs(remarks: str) -> None:
@@ -83,6 +115,9 @@ def check_w8_vgprs(remarks: str) -> None:
                                  "k_select could no longer co-reside with the ResNet kernel")
     if not seen:  # A/B builds with other geometries (e.g. -DOAMD_WC=128) have no w8 kernel
         sys.stderr.write("note: no k_resnet_w8 kernel in this build\n")
+
+
+RESOURCE_CHECKS = {"resnet.hip": check_w8_vgprs, "solver.hip": check_solver_scratch}
 
 
 def newer(out: Path, deps: list[Path]) -> bool:

@@ -21,6 +21,7 @@
 #include "engine.h"
 #include "kernels.h"
 #include "replay.h"
+#include "solver.h"
 #include "timing.h"
 
 using namespace oamd;
@@ -2083,6 +2084,79 @@ int oamd_replay_counters(const oamd_replay_view* view, int64_t* size, int64_t* h
     if (size) *size = c[kReplaySize];
     if (games_completed) *games_completed = c[kReplayGames];
     if (flags) *flags = (int32_t)c[kReplayFlags];
+    return OAMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Exact endgame solver (solver.h, solver.hip): the caller owns every buffer
+// ---------------------------------------------------------------------------
+static int solve_limit_checks(int32_t max_empties, int64_t node_limit) {
+    if (max_empties < 0 || max_empties > kSolveMaxEmpties)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= max_empties <= " + std::to_string(kSolveMaxEmpties) +
+                                               ", but got " + std::to_string(max_empties) + ".");
+    if (node_limit < 1 || node_limit >= (1LL << kSolveStatusShift))
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "Expected 1 <= node_limit < 2^56, but got " + std::to_string(node_limit) + ".");
+    return OAMD_OK;
+}
+
+int oamd_solve_workspace_bytes(int64_t n, int64_t* bytes) {
+    if (!bytes) return fail(OAMD_INVALID_ARGUMENT, "solve: bytes is NULL");
+    if (n < 0 || n > INT32_MAX / 65)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= n <= " + std::to_string(INT32_MAX / 65) + ", but got " +
+                                               std::to_string(n) + ".");
+    *bytes = solve_workspace_bytes(n);
+    return OAMD_OK;
+}
+
+static int solve_endgames(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
+                          int64_t node_limit, int32_t* move_scores_dev, int32_t* score_dev, int32_t* best_action_dev,
+                          int32_t* flags_dev, int64_t* nodes_dev, void* workspace_dev, int32_t workgroups,
+                          void* stream) {
+    static_assert(sizeof(oamd_position) == 40, "layout");
+    if (int rc = solve_limit_checks(max_empties, node_limit)) return rc;
+    if (n < 0 || n > INT32_MAX / 65)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= n <= " + std::to_string(INT32_MAX / 65) + ", but got " +
+                                               std::to_string(n) + ".");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess) n_dev = 0;
+    if (device < 0 || device >= n_dev) return fail(OAMD_INVALID_ARGUMENT, "solve: no HIP device " + std::to_string(device));
+    if (n == 0) return OAMD_OK;
+    if (!pos_dev || !move_scores_dev || !workspace_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "solve: positions, move_scores and workspace buffers are required");
+    DeviceGuard dg(device);
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    launch_solve(pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev, best_action_dev, flags_dev,
+                 nodes_dev, workspace_dev, workgroups, cus > 0 ? cus : 1, (hipStream_t)stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+int oamd_solve_endgames(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
+                        int64_t node_limit, int32_t* move_scores_dev, int32_t* score_dev, int32_t* best_action_dev,
+                        int32_t* flags_dev, int64_t* nodes_dev, void* workspace_dev, void* stream) {
+    return solve_endgames(device, pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev, best_action_dev,
+                          flags_dev, nodes_dev, workspace_dev, 0, stream);
+}
+
+int oamd_solve_endgames_grid(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
+                             int64_t node_limit, int32_t* move_scores_dev, int32_t* score_dev,
+                             int32_t* best_action_dev, int32_t* flags_dev, int64_t* nodes_dev, void* workspace_dev,
+                             int32_t workgroups, void* stream) {
+    if (workgroups < 1)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected workgroups >= 1, but got " + std::to_string(workgroups) + ".");
+    return solve_endgames(device, pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev, best_action_dev,
+                          flags_dev, nodes_dev, workspace_dev, workgroups, stream);
+}
+
+int oamd_host_solve_endgame(const oamd_position* pos_host, int32_t max_empties, int64_t node_limit,
+                            int32_t* move_scores65, int32_t* score, int32_t* best_action, int32_t* flags,
+                            int64_t* nodes) {
+    if (int rc = solve_limit_checks(max_empties, node_limit)) return rc;
+    if (!pos_host || !move_scores65) return fail(OAMD_INVALID_ARGUMENT, "solve: position and move_scores are required");
+    solve_host(pos_host->player, pos_host->player1_discs, pos_host->player2_discs, max_empties, node_limit,
+               move_scores65, score, best_action, flags, nodes);
     return OAMD_OK;
 }
 

@@ -791,6 +791,41 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
             return py::make_tuple(size, head, games, flags);
         });
 
+    // ---- exact endgame solver (othello_mcts/endgame.py) ----
+    m.def("_host_solve", [](int player, uint64_t p1, uint64_t p2, int max_empties, int64_t node_limit) {
+        oamd_position p{};
+        p.player = player;
+        p.player1_discs = p1;
+        p.player2_discs = p2;
+        int32_t ms[65], score = 0, best = 0, flags = 0;
+        int64_t nodes = 0;
+        check(oamd_host_solve_endgame(&p, max_empties, node_limit, ms, &score, &best, &flags, &nodes));
+        return py::make_tuple(std::vector<int>(ms, ms + 65), score, best, flags, nodes);
+    });
+    m.def("_solve_workspace_bytes", [](int64_t n) {
+        int64_t bytes = 0;
+        check(oamd_solve_workspace_bytes(n, &bytes));
+        return bytes;
+    });
+    // workgroups = 0: the product entry point; >= 1: the experimental one with that grid
+    m.def("_gpu_solve", [](int device, uintptr_t pos, int64_t n, int max_empties, int64_t node_limit,
+                           uintptr_t move_scores, uintptr_t score, uintptr_t best, uintptr_t flags, uintptr_t nodes,
+                           uintptr_t workspace, int workgroups, uintptr_t stream) {
+        auto* P = reinterpret_cast<const oamd_position*>(pos);
+        auto* ms = reinterpret_cast<int32_t*>(move_scores);
+        auto* sc = reinterpret_cast<int32_t*>(score);
+        auto* be = reinterpret_cast<int32_t*>(best);
+        auto* fl = reinterpret_cast<int32_t*>(flags);
+        auto* no = reinterpret_cast<int64_t*>(nodes);
+        void* ws = reinterpret_cast<void*>(workspace);
+        void* st = reinterpret_cast<void*>(stream);
+        if (workgroups == 0)
+            check(oamd_solve_endgames(device, P, n, max_empties, node_limit, ms, sc, be, fl, no, ws, st));
+        else
+            check(oamd_solve_endgames_grid(device, P, n, max_empties, node_limit, ms, sc, be, fl, no, ws, workgroups,
+                                           st));
+    });
+
     // GPU bitboard kernels over device buffers (data_ptr ints) for parity tests
     m.def("_gpu_legal_moves", [](uintptr_t me, uintptr_t opp, uintptr_t out, int64_t n, uintptr_t stream) {
         check(oamd_get_legal_moves((const uint64_t*)me, (const uint64_t*)opp, (uint64_t*)out, n, (void*)stream));

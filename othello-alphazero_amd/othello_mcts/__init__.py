@@ -12,7 +12,9 @@ the training step beside the engine (``SampleBuffer``, ``train_epoch``,
 ``alphazero_loss``, ``refresh_native``: train.py:455-521 with the samples kept
 in HBM) and ``ReplayBuffer`` / ``train_epoch_replay``: the same samples kept as
 packed positions (bitboards, 94 times smaller at H = 8) and expanded to the 8
-board symmetries when a minibatch is gathered.
+board symmetries when a minibatch is gathered. ``solve_endgames`` /
+``solve_position`` / ``endgame_move_loss`` solve the last plies exactly (GPU
+and host) and measure a move against perfect play.
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -36,6 +38,7 @@ from .arena import Arena, ArenaResult, paired_openings  # noqa: E402,F401
 from .native import NativeNet, load_checkpoint  # noqa: E402,F401
 from .selfplay import SelfPlayCollector, self_play  # noqa: E402,F401
 from .replay import ReplayBuffer  # noqa: E402,F401
+from .endgame import EndgameSolution, endgame_move_loss, solve_endgames, solve_position  # noqa: E402,F401
 from .training import (  # noqa: E402,F401
     SampleBuffer,
     alphazero_loss,
@@ -64,4 +67,8 @@ __all__ = [
     "Arena",
     "ArenaResult",
     "paired_openings",
+    "EndgameSolution",
+    "solve_endgames",
+    "solve_position",
+    "endgame_move_loss",
 ]

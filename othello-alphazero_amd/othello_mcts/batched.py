@@ -154,6 +154,15 @@ class BatchedMCTS:
         self.engine.root_stats(v.data_ptr(), q.data_ptr(), 0)
         return v, q
 
+    def root_positions(self) -> torch.Tensor:
+        """Every game's root as ``oamd_position``: (G, 5) int64 on the device
+        (player, the two disc sets, legal moves, the passer's opponent's
+        moves), what ``othello_mcts.solve_endgames`` takes. Enqueued only."""
+        self._stream()
+        info = torch.empty((self.num_games, 8), dtype=torch.int64, device=self.device)  # oamd_root_info: 64 bytes
+        self.engine.root_stats(0, 0, info.data_ptr())
+        return info[:, :5].contiguous()
+
     def self_play_data(self, game: int):
         self._stream()
         f, p = self.engine.self_play_data(game)
