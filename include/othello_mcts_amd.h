@@ -403,6 +403,42 @@ int oamd_replay_gather(const oamd_replay_view *view, const int64_t *ids_dev, int
 int oamd_replay_counters(const oamd_replay_view *view, int64_t *size, int64_t *head, int64_t *games_completed,
                          int32_t *flags, void *stream);
 
+/* Exact endgame value targets (optional). The caller keeps one more ring
+ * array beside the view, exact_dev (capacity) int8, initialised to
+ * OAMD_REPLAY_EXACT_UNKNOWN, and feeds the ring with oamd_replay_add_tracked.
+ * A slot's byte says where its value comes from: */
+#define OAMD_REPLAY_EXACT_UNKNOWN (-128) /* the game's outcome; not examined yet */
+#define OAMD_REPLAY_EXACT_GAVE_UP (-127) /* examined, not solved (node limit, invalid record): the game's */
+/* -64..64: the exact disc difference at the end of perfect play for the side
+ * to move in that record; the slot's value is its sign (-1, 0, +1). */
+#define OAMD_REPLAY_POLICY_KEEP 0    /* policy_mode: leave the policy row alone */
+#define OAMD_REPLAY_POLICY_OPTIMAL 1 /* 1/m on the m actions whose move_scores equal score, pass included */
+
+/* oamd_replay_add, and every ring slot it writes also gets
+ * exact_dev[slot] = OAMD_REPLAY_EXACT_UNKNOWN (same kernel, same lane). */
+int oamd_replay_add_tracked(const oamd_replay_view *view, int8_t *exact_dev, int32_t n_moves,
+                            const int32_t *actions_dev, const int32_t *finished_dev, const float *features_dev,
+                            const float *policy_dev, void *stream);
+/* bytes of the caller-owned workspace of a relabel call; budget in [1, 2^20] */
+int oamd_replay_relabel_workspace_bytes(int64_t budget, int64_t *bytes);
+/* Replace game outcomes by exact results where the solver reaches. Live
+ * positions are numbered from the oldest; a candidate has exact ==
+ * OAMD_REPLAY_EXACT_UNKNOWN (or OAMD_REPLAY_EXACT_GAVE_UP when retry != 0) and
+ * at most max_empties empty squares in history step 0. The first `budget`
+ * candidates are solved as {player + 1, boards[0], boards[1]} by
+ * oamd_solve_endgames with max_empties and node_limit. No flag: exact = the
+ * score for the mover (a terminal root's black-minus-white is negated for
+ * white), value = its sign, and with OAMD_REPLAY_POLICY_OPTIMAL a root with
+ * actions gets the optimal policy (transform-0 coordinates). Any flag: exact
+ * = OAMD_REPLAY_EXACT_GAVE_UP, value and policy untouched.
+ * relabel_counters_dev (4) int64, zero-initialised by the caller: [0]
+ * positions labelled so far, [1] positions given up so far, [2] candidates
+ * this call left behind for lack of budget, [3] candidates it took.
+ * Enqueued only; allocates nothing. */
+int oamd_replay_relabel_endgames(const oamd_replay_view *view, int8_t *exact_dev, int64_t *relabel_counters_dev,
+                                 int32_t max_empties, int64_t budget, int64_t node_limit, int32_t policy_mode,
+                                 int32_t retry, void *workspace_dev, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Exact endgame solver: the last plies solved by brute force on bitboards.  */
 /* Stands in for the external engine behind the reference's EgaroucidPlayer  */

@@ -2038,8 +2038,10 @@ static int replay_checks(const oamd_replay_view* v) {
     return OAMD_OK;
 }
 
-int oamd_replay_add(const oamd_replay_view* view, int32_t n_moves, const int32_t* actions_dev,
-                    const int32_t* finished_dev, const float* features_dev, const float* policy_dev, void* stream) {
+// exact_dev: the ring's exact bytes, or nullptr for a buffer that keeps none
+static int replay_add(const oamd_replay_view* view, int8_t* exact_dev, int32_t n_moves, const int32_t* actions_dev,
+                      const int32_t* finished_dev, const float* features_dev, const float* policy_dev,
+                      void* stream) {
     if (int rc = replay_checks(view)) return rc;
     if (n_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "replay: n_moves must be >= 0");
     if (n_moves == 0) return OAMD_OK;
@@ -2052,11 +2054,23 @@ int oamd_replay_add(const oamd_replay_view* view, int32_t n_moves, const int32_t
     const size_t G = (size_t)view->num_games;
     const size_t C = 1 + 2 * (size_t)view->history_size;
     for (int32_t i = 0; i < n_moves; ++i) {
-        launch_replay_add(*view, actions_dev + i * G, finished_dev + i * G, features_dev + i * G * 8 * C * 64,
-                          policy_dev + i * G * 8 * 65, (hipStream_t)stream);
+        launch_replay_add(*view, exact_dev, actions_dev + i * G, finished_dev + i * G,
+                          features_dev + i * G * 8 * C * 64, policy_dev + i * G * 8 * 65, (hipStream_t)stream);
         LAUNCHCHK();
     }
     return OAMD_OK;
+}
+
+int oamd_replay_add(const oamd_replay_view* view, int32_t n_moves, const int32_t* actions_dev,
+                    const int32_t* finished_dev, const float* features_dev, const float* policy_dev, void* stream) {
+    return replay_add(view, nullptr, n_moves, actions_dev, finished_dev, features_dev, policy_dev, stream);
+}
+
+int oamd_replay_add_tracked(const oamd_replay_view* view, int8_t* exact_dev, int32_t n_moves,
+                            const int32_t* actions_dev, const int32_t* finished_dev, const float* features_dev,
+                            const float* policy_dev, void* stream) {
+    if (!exact_dev) return fail(OAMD_INVALID_ARGUMENT, "replay: the exact buffer is required");
+    return replay_add(view, exact_dev, n_moves, actions_dev, finished_dev, features_dev, policy_dev, stream);
 }
 
 int oamd_replay_gather(const oamd_replay_view* view, const int64_t* ids_dev, int64_t n, float* features_dev,
@@ -2157,6 +2171,47 @@ int oamd_host_solve_endgame(const oamd_position* pos_host, int32_t max_empties, 
     if (!pos_host || !move_scores65) return fail(OAMD_INVALID_ARGUMENT, "solve: position and move_scores are required");
     solve_host(pos_host->player, pos_host->player1_discs, pos_host->player2_discs, max_empties, node_limit,
                move_scores65, score, best_action, flags, nodes);
+    return OAMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Exact endgame value targets of the packed replay buffer (replay.hip + solver.hip)
+// ---------------------------------------------------------------------------
+constexpr int64_t kRelabelMaxBudget = 1 << 20;
+
+static int relabel_budget_check(int64_t budget) {
+    if (budget < 1 || budget > kRelabelMaxBudget)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 1 <= budget <= " + std::to_string(kRelabelMaxBudget) +
+                                               ", but got " + std::to_string(budget) + ".");
+    return OAMD_OK;
+}
+
+int oamd_replay_relabel_workspace_bytes(int64_t budget, int64_t* bytes) {
+    if (!bytes) return fail(OAMD_INVALID_ARGUMENT, "replay: bytes is NULL");
+    if (int rc = relabel_budget_check(budget)) return rc;
+    *bytes = relabel_workspace_bytes(budget);
+    return OAMD_OK;
+}
+
+int oamd_replay_relabel_endgames(const oamd_replay_view* view, int8_t* exact_dev, int64_t* relabel_counters_dev,
+                                 int32_t max_empties, int64_t budget, int64_t node_limit, int32_t policy_mode,
+                                 int32_t retry, void* workspace_dev, void* stream) {
+    if (int rc = solve_limit_checks(max_empties, node_limit)) return rc;
+    if (int rc = relabel_budget_check(budget)) return rc;
+    if (policy_mode != OAMD_REPLAY_POLICY_KEEP && policy_mode != OAMD_REPLAY_POLICY_OPTIMAL)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "Expected policy_mode 0 (keep) or 1 (optimal), but got " + std::to_string(policy_mode) + ".");
+    if (int rc = replay_checks(view)) return rc;
+    if (view->capacity > INT32_MAX)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: relabelling needs capacity < 2^31");
+    if (!exact_dev || !relabel_counters_dev || !workspace_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "replay: exact, relabel_counters and workspace buffers are required");
+    DeviceGuard dg(view->device);
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, view->device));
+    launch_replay_relabel(*view, exact_dev, relabel_counters_dev, max_empties, budget, node_limit, policy_mode,
+                          retry != 0, workspace_dev, cus > 0 ? cus : 1, (hipStream_t)stream);
+    LAUNCHCHK();
     return OAMD_OK;
 }
 

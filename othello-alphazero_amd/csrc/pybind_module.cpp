@@ -777,6 +777,25 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                                        reinterpret_cast<const int32_t*>(finished), reinterpret_cast<const float*>(feat),
                                        reinterpret_cast<const float*>(pol), reinterpret_cast<void*>(stream)));
              })
+        .def("add_tracked",
+             [](const oamd_replay_view& v, uintptr_t exact, int n_moves, uintptr_t actions, uintptr_t finished,
+                uintptr_t feat, uintptr_t pol, uintptr_t stream) {
+                 check(oamd_replay_add_tracked(&v, reinterpret_cast<int8_t*>(exact), n_moves,
+                                               reinterpret_cast<const int32_t*>(actions),
+                                               reinterpret_cast<const int32_t*>(finished),
+                                               reinterpret_cast<const float*>(feat),
+                                               reinterpret_cast<const float*>(pol), reinterpret_cast<void*>(stream)));
+             })
+        .def("relabel",
+             [](const oamd_replay_view& v, uintptr_t exact, uintptr_t relabel_counters, int max_empties,
+                int64_t budget, int64_t node_limit, int policy_mode, bool retry, uintptr_t workspace,
+                uintptr_t stream) {
+                 check(oamd_replay_relabel_endgames(&v, reinterpret_cast<int8_t*>(exact),
+                                                    reinterpret_cast<int64_t*>(relabel_counters), max_empties, budget,
+                                                    node_limit, policy_mode, retry ? 1 : 0,
+                                                    reinterpret_cast<void*>(workspace),
+                                                    reinterpret_cast<void*>(stream)));
+             })
         .def("gather",
              [](const oamd_replay_view& v, uintptr_t ids, int64_t n, uintptr_t feat, uintptr_t pol, uintptr_t val,
                 uintptr_t stream) {
@@ -801,6 +820,11 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
         int64_t nodes = 0;
         check(oamd_host_solve_endgame(&p, max_empties, node_limit, ms, &score, &best, &flags, &nodes));
         return py::make_tuple(std::vector<int>(ms, ms + 65), score, best, flags, nodes);
+    });
+    m.def("_relabel_workspace_bytes", [](int64_t budget) {
+        int64_t bytes = 0;
+        check(oamd_replay_relabel_workspace_bytes(budget, &bytes));
+        return bytes;
     });
     m.def("_solve_workspace_bytes", [](int64_t n) {
         int64_t bytes = 0;

@@ -11,13 +11,25 @@
 //   k_replay_gather  one wave per sample: position id >> 3 under transform
 //                    id & 7 as fp32 planes, policy and value
 //
-// Every kernel reads only what earlier launches wrote (commit keeps its prefix
-// sum in LDS), so no load depends on a store of the same launch.
+// Exact endgame value targets, for a ring that also keeps one
+// `exact` byte per slot:
+//
+//   k_replay_endgame_list   one block: the live positions in age order whose
+//                           exact byte asks for it and that have few empties,
+//                           ranked by a prefix sum; the first `budget` of them
+//                           become a list of oamd_position rows for the solver
+//                           (solver.hip, next in stream order)
+//   k_replay_endgame_apply  one wave per list row: the solver's answer becomes
+//                           the slot's exact byte, value and (optionally) policy
+//
+// Every kernel reads only what earlier launches wrote (commit and list keep
+// their prefix sums in LDS), so no load depends on a store of the same launch.
 
 #include <hip/hip_runtime.h>
 
 #include "bitboard.h"
 #include "replay.h"
+#include "solver.h"
 
 namespace oamd {
 
@@ -94,7 +106,9 @@ __device__ __forceinline__ int wave_scan(int v, int lane) {
 // positions are committed at once, only the last `capacity` are written, so
 // no slot has two writers. Value rule of SampleBuffer: the outcome for black
 // (bits 0-1: 1 draw, 2 black won, 3 white won), negated when white is to move.
-__global__ __launch_bounds__(kCommitThreads) void k_replay_commit(oamd_replay_view V, const int32_t* finished) {
+// exact: the ring's exact bytes, or nullptr for a buffer that keeps none.
+__global__ __launch_bounds__(kCommitThreads) void k_replay_commit(oamd_replay_view V, const int32_t* finished,
+                                                                  int8_t* exact) {
     __shared__ int s_off[kCommitThreads];
     __shared__ int s_n[kCommitThreads];
     __shared__ float s_outcome[kCommitThreads];
@@ -175,6 +189,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_replay_commit(oamd_replay_vi
                     const uint8_t white = V.stage_player[rec];
                     V.player[slot] = white;
                     V.value[slot] = outcome * (white ? -1.0f : 1.0f);
+                    if (exact) exact[slot] = OAMD_REPLAY_EXACT_UNKNOWN;  // the game's outcome, not examined
                 }
             }
         }
@@ -230,12 +245,139 @@ __global__ __launch_bounds__(64 * kGatherWaves) void k_replay_gather(oamd_replay
     }
 }
 
+// The solver's cheapest row: overlapping discs, which solve_classify refuses in
+// its first test, before any move generation. Its 65 slots cost one
+// classification each and no search; apply skips the row by its slot of -1.
+__device__ __forceinline__ void put_pad(oamd_position* p) {
+    p->player = 1;
+    p->reserved = 0;
+    p->player1_discs = p->player2_discs = ~0ULL;
+    p->legal_moves = p->next_legal_moves = 0;
+}
+
+// One block. Live position i (0 = oldest) sits in slot (head - size + i) mod
+// capacity. Per chunk of 1024 positions: candidate bit, inclusive scan over the
+// wave, per-wave totals in LDS, a running carry: rank = candidates before i.
+// Rows rank < budget get the position and its slot; the scan goes on to the
+// end, because rc[2] counts what the budget left behind. Rows taken..budget-1
+// are padded. Writes the two lists and rc[2], rc[3] only.
+__global__ __launch_bounds__(kCommitThreads) void k_replay_endgame_list(oamd_replay_view V, const int8_t* exact,
+                                                                        int64_t* rc, int32_t max_empties,
+                                                                        int64_t budget, int32_t retry,
+                                                                        oamd_position* pos, int32_t* slots) {
+    __shared__ int s_wave[kCommitWaves];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int H2 = 2 * V.history_size;
+    const int64_t cap = V.capacity;
+    const int64_t head = V.counters[kReplayHead];
+    const int64_t size = V.counters[kReplaySize];
+    int64_t carry = 0;
+    for (int64_t base = 0; base < size; base += kCommitThreads) {
+        const int64_t i = base + tid;
+        int64_t slot = head - size + i;
+        if (slot < 0) slot += cap;
+        uint64_t b1 = 0, b2 = 0;
+        int cand = 0;
+        if (i < size) {
+            const int8_t e = exact[slot];
+            if (e == OAMD_REPLAY_EXACT_UNKNOWN || (retry && e == OAMD_REPLAY_EXACT_GAVE_UP)) {
+                b1 = V.boards[(size_t)slot * H2];  // history step 0: black's discs, white's discs
+                b2 = V.boards[(size_t)slot * H2 + 1];
+                cand = 64 - popcount64(b1 | b2) <= max_empties;
+            }
+        }
+        const int incl = wave_scan(cand, lane);
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int woff = 0, chunk = 0;
+        for (int w = 0; w < kCommitWaves; ++w) {
+            if (w < wave) woff += s_wave[w];
+            chunk += s_wave[w];
+        }
+        const int64_t rank = carry + woff + incl - cand;
+        if (cand && rank < budget) {
+            oamd_position* p = pos + rank;
+            p->player = V.player[slot] + 1;
+            p->reserved = 0;
+            p->player1_discs = b1;
+            p->player2_discs = b2;
+            p->legal_moves = p->next_legal_moves = 0;
+            slots[rank] = (int32_t)slot;
+        }
+        carry += chunk;
+        __syncthreads();  // s_wave is rewritten by the next chunk
+    }
+    const int64_t taken = carry < budget ? carry : budget;
+    for (int64_t r = taken + tid; r < budget; r += kCommitThreads) {
+        put_pad(pos + r);
+        slots[r] = -1;
+    }
+    if (tid == 0) {
+        rc[kRelabelLeft] = carry - taken;
+        rc[kRelabelTaken] = taken;
+    }
+}
+
+// Wave w of block b = list row b * 4 + w. Lane l owns policy entry l, lane 0
+// also entry 64. A flagged row (node limit, invalid record) marks the slot and
+// leaves its value and policy alone. A terminal root (best_action -1) reports
+// black minus white: negated for white, and no policy to write.
+__global__ __launch_bounds__(64 * kGatherWaves) void k_replay_endgame_apply(
+    oamd_replay_view V, int8_t* exact, int64_t* rc, int64_t budget, int32_t policy_mode, const int32_t* slots,
+    const int32_t* move_scores, const int32_t* score, const int32_t* best_action, const int32_t* flags) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kGatherWaves + (threadIdx.x >> 6);
+    if (r >= budget) return;
+    const int32_t slot = slots[r];
+    if (slot < 0) return;  // pad row
+    if (flags[r] != 0) {
+        if (lane == 0) {
+            exact[slot] = OAMD_REPLAY_EXACT_GAVE_UP;
+            atomicAdd(reinterpret_cast<unsigned long long*>(rc + kRelabelGaveUp), 1ULL);
+        }
+        return;
+    }
+    const int32_t sc = score[r];
+    const bool searched = best_action[r] >= 0;
+    if (policy_mode == OAMD_REPLAY_POLICY_OPTIMAL && searched) {
+        const int32_t* ms = move_scores + r * 65;
+        const bool mine = ms[lane] == sc;
+        const bool pass = ms[64] == sc;
+        const int m = popcount64(__ballot(mine)) + (pass ? 1 : 0);
+        const float w = 1.0f / (float)m;  // m >= 1: best_action is one of them
+        float* p = V.policy + (size_t)slot * 65;
+        p[lane] = mine ? w : 0.0f;
+        if (lane == 0) p[64] = pass ? w : 0.0f;
+    }
+    if (lane == 0) {
+        const int32_t s = searched || !V.player[slot] ? sc : -sc;
+        exact[slot] = (int8_t)s;
+        V.value[slot] = s > 0 ? 1.0f : (s < 0 ? -1.0f : 0.0f);
+        atomicAdd(reinterpret_cast<unsigned long long*>(rc + kRelabelSolved), 1ULL);
+    }
+}
+
 }  // namespace
 
-void launch_replay_add(const oamd_replay_view& V, const int32_t* actions, const int32_t* finished,
+void launch_replay_add(const oamd_replay_view& V, int8_t* exact, const int32_t* actions, const int32_t* finished,
                        const float* features, const float* policy, hipStream_t s) {
     hipLaunchKernelGGL(k_replay_add, dim3(V.num_games), dim3(64), 0, s, V, actions, finished, features, policy);
-    hipLaunchKernelGGL(k_replay_commit, dim3(1), dim3(kCommitThreads), 0, s, V, finished);
+    hipLaunchKernelGGL(k_replay_commit, dim3(1), dim3(kCommitThreads), 0, s, V, finished, exact);
+}
+
+void launch_replay_relabel(const oamd_replay_view& V, int8_t* exact, int64_t* relabel_counters, int32_t max_empties,
+                           int64_t budget, int64_t node_limit, int32_t policy_mode, int32_t retry, void* workspace,
+                           int32_t compute_units, hipStream_t s) {
+    const RelabelWorkspace w(workspace, budget);
+    hipLaunchKernelGGL(k_replay_endgame_list, dim3(1), dim3(kCommitThreads), 0, s, V, exact, relabel_counters,
+                       max_empties, budget, retry, w.pos, w.slots);
+    launch_solve(w.pos, budget, max_empties, node_limit, w.move_scores, w.score, w.best_action, w.flags, nullptr,
+                 w.solver, 0, compute_units, s);
+    const unsigned blocks = (unsigned)((budget + kGatherWaves - 1) / kGatherWaves);
+    hipLaunchKernelGGL(k_replay_endgame_apply, dim3(blocks), dim3(64 * kGatherWaves), 0, s, V, exact,
+                       relabel_counters, budget, policy_mode, w.slots, w.move_scores, w.score, w.best_action, w.flags);
 }
 
 void launch_replay_gather(const oamd_replay_view& V, const int64_t* ids, int64_t n, float* features,

@@ -14,7 +14,9 @@ in HBM) and ``ReplayBuffer`` / ``train_epoch_replay``: the same samples kept as
 packed positions (bitboards, 94 times smaller at H = 8) and expanded to the 8
 board symmetries when a minibatch is gathered. ``solve_endgames`` /
 ``solve_position`` / ``endgame_move_loss`` solve the last plies exactly (GPU
-and host) and measure a move against perfect play.
+and host) and measure a move against perfect play;
+``ReplayBuffer(track_exact=True).relabel_endgames`` uses the same solver to
+give the buffer's last plies exact value targets.
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.

@@ -15,20 +15,47 @@ oldest-first order.
 
 The storage is plain torch tensors on the engine's device (structure of
 arrays), so a checkpoint is ``state_dict()``.
+
+``track_exact=True`` adds one byte per slot (``exact``) and
+``relabel_endgames``: the positions with few empties get the exact result of
+perfect play (csrc/solver.hip) as their value target instead of the outcome of
+the game they came from. Off by default, and then nothing here
+behaves, stores or serialises differently.
 """
 
 from __future__ import annotations
 
 import torch
 
-from ._othello_mcts_impl import _ReplayView
+from ._othello_mcts_impl import _relabel_workspace_bytes, _ReplayView
+from .endgame import DEFAULT_NODE_LIMIT, _check_limits
 
 # sticky bits of the device counter block (include/othello_mcts_amd.h OAMD_REPLAY_*)
 FLAG_OVERFLOW, FLAG_NO_TARGETS, FLAG_TOO_LONG, FLAG_BAD_ID = 1, 2, 4, 8
 
+# codes of the ``exact`` ring (include/othello_mcts_amd.h OAMD_REPLAY_EXACT_*); -64..64 is an exact score
+EXACT_UNKNOWN, EXACT_GAVE_UP = -128, -127
+MAX_BUDGET = 1 << 20
+_POLICY_MODES = {"keep": 0, "optimal": 1}
+
 _RING = ("boards", "policy", "value", "player")
+_EXACT = ("exact", "relabel_counters")
 _STAGE = ("stage_boards", "stage_policy", "stage_player", "moves")
 _DIMS = ("num_games", "history_size", "capacity", "max_moves")
+
+
+def _check_relabel(max_empties, budget, node_limit, policy, retry) -> None:
+    _check_limits(max_empties, node_limit)
+    if isinstance(budget, bool) or not isinstance(budget, int):
+        raise TypeError(f"Expected an int for budget, but got {type(budget).__name__}.")
+    if not isinstance(policy, str):
+        raise TypeError(f"Expected a str for policy, but got {type(policy).__name__}.")
+    if not isinstance(retry, bool):
+        raise TypeError(f"Expected a bool for retry, but got {type(retry).__name__}.")
+    if not 1 <= budget <= MAX_BUDGET:
+        raise ValueError(f"Expected 1 <= budget <= {MAX_BUDGET}, but got {budget}.")
+    if policy not in _POLICY_MODES:
+        raise ValueError(f"Expected policy 'keep' or 'optimal', but got {policy!r}.")
 
 
 def _validate(num_games, history_size, capacity, max_moves) -> None:
@@ -57,11 +84,19 @@ class ReplayBuffer:
     staging area until the game finishes; then they get their value targets
     (``SampleBuffer``'s rule) and move into the ring in ascending game order,
     the oldest positions overwritten. Rows the kernels refuse set sticky flags;
-    ``check()`` raises them with ``SampleBuffer``'s messages."""
+    ``check()`` raises them with ``SampleBuffer``'s messages.
+
+    ``track_exact=True``: the ring also keeps ``exact`` (``capacity`` int8:
+    ``EXACT_UNKNOWN``, ``EXACT_GAVE_UP`` or the exact disc difference for the
+    side to move) and ``relabel_counters``, and ``relabel_endgames`` works."""
 
     def __init__(self, num_games: int, history_size: int, capacity: int, max_moves: int = 128,
-                 device: torch.device | str | None = None) -> None:
+                 device: torch.device | str | None = None, track_exact: bool = False) -> None:
         _validate(num_games, history_size, capacity, max_moves)
+        if not isinstance(track_exact, bool):
+            raise TypeError(f"Expected a bool for track_exact, but got {type(track_exact).__name__}.")
+        if track_exact and capacity >= 1 << 31:
+            raise ValueError(f"Expected capacity < 2^31 with track_exact, but got {capacity}.")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         device = torch.device(device)
@@ -86,6 +121,12 @@ class ReplayBuffer:
         self._pending = torch.zeros((G,), dtype=torch.int32, device=d)
         # head, size, games_completed, sticky flags
         self.counters = torch.zeros((4,), dtype=torch.int64, device=d)
+        self.track_exact = track_exact
+        if track_exact:
+            self.exact = torch.full((capacity,), EXACT_UNKNOWN, dtype=torch.int8, device=d)
+            # labelled so far, given up so far, left behind by the last call, taken by the last call
+            self.relabel_counters = torch.zeros((4,), dtype=torch.int64, device=d)
+            self._relabel_ws: dict[int, torch.Tensor] = {}  # workspace per budget
 
     # ------------------------------------------------------------------ plumbing
     def _view(self) -> _ReplayView:
@@ -119,8 +160,51 @@ class ReplayBuffer:
         finished = self._input(out, "finished", torch.int32, (G,), lead)
         features = self._input(out, "features", torch.float32, (G, 8, self.C, 8, 8), lead)
         policy = self._input(out, "policy", torch.float32, (G, 8, 65), lead)
-        self._view().add(lead[0] if lead else 1, actions.data_ptr(), finished.data_ptr(), features.data_ptr(),
-                         policy.data_ptr(), self._stream())
+        n = lead[0] if lead else 1
+        if self.track_exact:
+            self._view().add_tracked(self.exact.data_ptr(), n, actions.data_ptr(), finished.data_ptr(),
+                                     features.data_ptr(), policy.data_ptr(), self._stream())
+        else:
+            self._view().add(n, actions.data_ptr(), finished.data_ptr(), features.data_ptr(), policy.data_ptr(),
+                             self._stream())
+
+    # ------------------------------------------------------------------ exact endgame targets
+    def relabel_endgames(self, max_empties: int = 10, budget: int = 4096, node_limit: int = DEFAULT_NODE_LIMIT,
+                         policy: str = "keep", retry: bool = False) -> None:
+        """Give the live positions with at most ``max_empties`` empties their
+        exact value target: the sign of the result of perfect play for the side
+        to move, from ``solve_endgames``' kernels. Oldest first, at most
+        ``budget`` positions per call; a position is examined once (again with
+        ``retry`` if the solver gave up on it: ``node_limit``, an invalid
+        record). ``policy="optimal"`` also replaces the policy row by the
+        uniform distribution over the optimal actions. Enqueues only."""
+        _check_relabel(max_empties, budget, node_limit, policy, retry)
+        if not self.track_exact:
+            raise RuntimeError("ReplayBuffer.relabel_endgames needs a buffer created with track_exact=True.")
+        ws = self._relabel_ws.get(budget)
+        if ws is None:
+            ws = torch.empty((_relabel_workspace_bytes(budget),), dtype=torch.uint8, device=self.device)
+            self._relabel_ws[budget] = ws
+        self._view().relabel(self.exact.data_ptr(), self.relabel_counters.data_ptr(), max_empties, budget, node_limit,
+                             _POLICY_MODES[policy], retry, ws.data_ptr(), self._stream())
+
+    @property
+    def relabel_stats(self) -> dict[str, int]:
+        """``relabel_counters`` as a dict (waits for the stream): positions
+        ``solved`` and ``gave_up`` so far, candidates the last call ``left``
+        behind for lack of budget and candidates it ``taken``."""
+        if not self.track_exact:
+            raise RuntimeError("ReplayBuffer.relabel_stats needs a buffer created with track_exact=True.")
+        return dict(zip(("solved", "gave_up", "left", "taken"), self.relabel_counters.tolist()))
+
+    def exact_scores(self) -> torch.Tensor:
+        """``exact`` of the live positions, oldest first (a device tensor of
+        ``size`` int8; reading the size waits for the stream)."""
+        if not self.track_exact:
+            raise RuntimeError("ReplayBuffer.exact_scores needs a buffer created with track_exact=True.")
+        size, head = self._counters()[:2]
+        slots = (head - size + torch.arange(size, device=self.device)) % self.capacity
+        return self.exact[slots]
 
     # ------------------------------------------------------------------ counters
     def _counters(self) -> tuple[int, int, int, int]:
@@ -148,7 +232,8 @@ class ReplayBuffer:
         the per-game move counts and commit scratch, the counter block)."""
         H = self.history_size
         staging = self.num_games * self.max_moves * (16 * H + 261) + 8 * self.num_games + 32
-        return self.capacity * (16 * H + 265) + staging
+        exact = self.capacity + 32 if self.track_exact else 0  # one byte per slot, the relabel counters
+        return self.capacity * (16 * H + 265) + staging + exact
 
     def check(self) -> None:
         """Raise what the kernels flagged since the buffer was created (waits
@@ -207,16 +292,23 @@ class ReplayBuffer:
     def state_dict(self) -> dict:
         """CPU copies of the ring, the staging area and the counters, and the
         dimensions (waits for the stream)."""
-        sd = {k: getattr(self, k).cpu() for k in _RING + _STAGE + ("counters",)}
+        sd = {k: getattr(self, k).cpu() for k in self._tensors()}
         sd.update({k: getattr(self, k) for k in _DIMS})
         return sd
+
+    def _tensors(self) -> tuple[str, ...]:
+        return _RING + _STAGE + ("counters",) + (_EXACT if self.track_exact else ())
 
     def load_state_dict(self, sd: dict) -> None:
         for k in _DIMS:
             if k not in sd or int(sd[k]) != getattr(self, k):
                 raise ValueError(f"ReplayBuffer.load_state_dict: {k} is {sd.get(k)!r} in the state, but "
                                  f"{getattr(self, k)} in this buffer.")
-        for k in _RING + _STAGE + ("counters",):
+        for k in _EXACT:
+            if (k in sd) != self.track_exact:
+                raise ValueError(f"ReplayBuffer.load_state_dict: the state {'has' if k in sd else 'lacks'} {k}, but "
+                                 f"this buffer was created with track_exact={self.track_exact}.")
+        for k in self._tensors():
             dst = getattr(self, k)
             src = sd[k]
             if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
@@ -229,8 +321,16 @@ class ReplayBuffer:
                              f"{self.capacity} positions.")
         if self.num_games and (int(sd["moves"].min()) < 0 or int(sd["moves"].max()) > self.max_moves):
             raise ValueError("ReplayBuffer.load_state_dict: a staged move count outside [0, max_moves].")
-        for k in _RING + _STAGE + ("counters",):
+        if self.track_exact:
+            e = sd["exact"].to(torch.int16)
+            if bool(((e > EXACT_GAVE_UP) & ((e < -64) | (e > 64))).any()):
+                raise ValueError("ReplayBuffer.load_state_dict: an exact code outside EXACT_UNKNOWN, EXACT_GAVE_UP "
+                                 "and [-64, 64].")
+            if int(sd["relabel_counters"].min()) < 0:
+                raise ValueError("ReplayBuffer.load_state_dict: a negative relabel counter.")
+        for k in self._tensors():
             getattr(self, k).copy_(sd[k])
 
 
-__all__ = ["ReplayBuffer", "FLAG_OVERFLOW", "FLAG_NO_TARGETS", "FLAG_TOO_LONG", "FLAG_BAD_ID"]
+__all__ = ["ReplayBuffer", "FLAG_OVERFLOW", "FLAG_NO_TARGETS", "FLAG_TOO_LONG", "FLAG_BAD_ID",
+           "EXACT_UNKNOWN", "EXACT_GAVE_UP", "MAX_BUDGET"]

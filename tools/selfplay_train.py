@@ -12,12 +12,18 @@ trained net's are (trees of a trained net concentrate and
 descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
-Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds] [packed]
+Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds] [packed [exact=K]]
 
 packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
 million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
 self-play phase; minibatches expanded by train_epoch_replay) instead of the
 fp32 SampleBuffer (400,000 samples in 1.85 GB, one add per move).
+
+exact=K (with packed): after each self-play phase and before training, the
+buffer's positions with at most K empties get the exact result of perfect play
+as their value target (ReplayBuffer.relabel_endgames). The
+iteration's log line gains relabel_ms (device events around the call) and the
+buffer's relabel_stats.
 """
 
 import json
@@ -83,6 +89,9 @@ def main():
     iterations = int(sys.argv[2]) if len(sys.argv) > 2 else 40
     G = int(sys.argv[3]) if len(sys.argv) > 3 else 256
     packed = "packed" in sys.argv[5:]
+    exact = [int(w[6:]) for w in sys.argv[5:] if w.startswith("exact=")]
+    if exact and not packed:
+        raise SystemExit("exact=K needs the packed buffer")
     moves_per_iter = 64
     torch.manual_seed(0)
     dev = torch.device("cuda", 0)
@@ -95,7 +104,7 @@ def main():
                        dirichlet_epsilon=0.25, dirichlet_alpha=0.5, seed=77)
     b.reset()
     if packed:
-        buf = om.ReplayBuffer(G, 8, capacity=500_000, device=dev)
+        buf = om.ReplayBuffer(G, 8, capacity=500_000, device=dev, track_exact=bool(exact))
     else:
         buf = om.SampleBuffer(G, 17, capacity=400_000, device=dev)
     log = []
@@ -114,6 +123,16 @@ def main():
                     buf.add({k: v[i] for k, v in o.items()})
         torch.cuda.synchronize()
         t1 = time.time()
+        selfplay_s = round(t1 - t0, 2)
+        relabel = {}
+        if exact:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            buf.relabel_endgames(exact[0])
+            e1.record()
+            stats = buf.relabel_stats  # the iteration's one host wait for the relabel
+            relabel = {"relabel_ms": round(e0.elapsed_time(e1), 2), "relabel": stats}
+            t1 = time.time()  # train_s starts after the relabel
         if packed:
             buf.check()
             n = 8 * buf.size
@@ -126,8 +145,8 @@ def main():
         om.refresh_native(native, model)
         torch.cuda.synchronize()
         rec = {"iteration": it, "games": buf.games_completed, "new_games": buf.games_completed - games0,
-               "samples": n, "selfplay_s": round(t1 - t0, 2), "train_s": round(time.time() - t1, 2),
-               **{k: round(v, 4) for k, v in losses.items()}}
+               "samples": n, "selfplay_s": selfplay_s, "train_s": round(time.time() - t1, 2),
+               **relabel, **{k: round(v, 4) for k, v in losses.items()}}
         log.append(rec)
         print(json.dumps(rec), flush=True)
         if time.time() - t_start > (float(sys.argv[4]) if len(sys.argv) > 4 else 900.0):
@@ -137,7 +156,8 @@ def main():
                                              for k, v in sd.items()})
     Path(str(out) + ".json").write_text(json.dumps({"iterations": log, "games_per_engine": G,
                                                     "moves_per_iteration": moves_per_iter,
-                                                    "buffer": "packed" if packed else "fp32"}, indent=1))
+                                                    "buffer": "packed" if packed else "fp32",
+                                                    "exact_max_empties": exact[0] if exact else None}, indent=1))
 
 
 if __name__ == "__main__":
