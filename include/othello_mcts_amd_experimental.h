@@ -51,7 +51,11 @@ int oamd_engine_set_chain_split(oamd_engine *e, int32_t budget, int32_t cuts);
  * the most cuts u any game used + min_rounds (2X + 2 + min_rounds when a
  * game ran out of cuts). Extra rounds past every game's last cut are empty
  * launches; a game that would need more cuts runs its last chain uncut.
- * enable = 0: X = cuts always. Scheduling only: results are identical. */
+ * enable = 0: X = cuts always. Scheduling only: results are identical.
+ * (The rule is AdaptiveRounds in csrc/schedule.h. A search that used cuts
+ * also raises the 12 to its fewest empties + 3 before the comparison, so it
+ * counts as endgame itself; the threshold then falls by one per search
+ * without cuts, back to 12.) */
 int oamd_engine_set_adaptive_extra_rounds(oamd_engine *e, int32_t enable, int32_t min_rounds);
 /* Workgroups of the chain-splitting extra rounds' ResNet launches (default
  * 128; 0 = the regular grid, the list's capacity): those launches hold the

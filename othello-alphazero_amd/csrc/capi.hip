@@ -21,12 +21,11 @@
 #include "engine.h"
 #include "kernels.h"
 #include "replay.h"
+#include "schedule.h"
 #include "solver.h"
 #include "timing.h"
 
 using namespace oamd;
-
-constexpr int kMaxPipeline = 8;
 
 // Host waits for a readback (the adaptive extra rounds' cut counts, the
 // free-running call's remaining-games counters and its enqueue throttle):
@@ -60,20 +59,6 @@ constexpr int kEvPerBlock = 4;  // timing events per (round, group): tree begin/
 // [7] deepest descent, [8..11] the tree work of oamd_engine_tree_work
 // (children scanned, expansions, children created, tree launches)
 constexpr int kCounters = 12;
-// Order of the pipeline groups' NN launches within an NN chain (one chain:
-// one after another, each owning every CU while the other groups' tree
-// kernels run beside it). OAMD_NN_ORDER 1: a token event passed between the
-// group streams; 2: all NN launches on one NN stream (a group's launch waits
-// for its select, its backup for the launch); 0: unordered (A/B only). Kernel
-// traces show the same gap between consecutive launches for 1 and 2 (~14 us,
-// ~24 us with the timing events), and 1 measured 0.4 % faster in the bench.
-// The default is one chain per group (2 groups, 2 chains): a group's launch
-// starts as soon as its selection is done, so it fills the other launch's
-// last-generation tail and the launch gap (bench +2.5-2.8 %, two boxes;
-// DESIGN.md §7).
-#ifndef OAMD_NN_ORDER
-#define OAMD_NN_ORDER 1
-#endif
 
 namespace {
 
@@ -122,6 +107,43 @@ void dfree(T*& p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+
+// Values the host reads back late: a device array, its pinned host mirror,
+// and an event per (slot, pipeline group) behind each copy into the mirror.
+struct ReadbackSlots {
+    static constexpr int kSlots = 4;
+    int32_t* dev = nullptr;
+    int32_t* host = nullptr;  // pinned
+    hipEvent_t ev[kSlots][kMaxPipeline] = {};
+    // allocated into a local and published only when every allocation
+    // succeeded (a failure leaves nothing half-initialised behind)
+    int ensure(size_t dev_words, size_t host_words, const char* what) {
+        if (dev) return OAMD_OK;
+        ReadbackSlots t;
+        int rc = dalloc(&t.dev, dev_words);
+        if (!rc && hipHostMalloc((void**)&t.host, sizeof(int32_t) * host_words) != hipSuccess)
+            rc = fail(OAMD_RUNTIME, std::string(what) + ": hipHostMalloc failed");
+        for (auto& row : t.ev)
+            for (auto& x : row)
+                if (!rc && hipEventCreateWithFlags(&x, readback_event_flags()) != hipSuccess)
+                    rc = fail(OAMD_RUNTIME, std::string(what) + ": hipEventCreate failed");
+        if (rc) t.release();
+        else *this = t;
+        return rc;
+    }
+    void release() {
+        for (auto& row : ev)
+            for (auto x : row)
+                if (x) (void)hipEventDestroy(x);
+        if (host) (void)hipHostFree(host);
+        dfree(dev);
+    }
+    void destroy() {
+        if (!dev) return;
+        (void)hipDeviceSynchronize();  // no copy into the pinned mirror in flight
+        release();
+    }
+};
 
 std::string fstr(float v) { return std::to_string(v); }
 
@@ -211,53 +233,15 @@ struct oamd_engine {
     // budget 0 = never split
     int chain_budget = 2;
     int chain_cuts = 64;
-    // adaptive extra rounds (pick_extra_rounds): a grouped search runs X in
-    // [min(adapt_min, chain_cuts), chain_cuts] extra rounds (and allows X
-    // cuts), X following the search two back. adapt_on = false: always
-    // chain_cuts
-    static constexpr int kCutSlots = 4;
-    bool adapt_on = true;
-    int adapt_min = 1;
-    int adapt_x = -1;        // the last X picked from a measurement (-1: none yet: the minimum)
-    // endgame threshold: at most this many empty squares on some game's root
-    // (two moves before the search) -> X = chain_cuts; raised past every root
-    // whose search needed cuts
-    static constexpr int kEndgameEmpties = 12;
-    int adapt_empties = kEndgameEmpties;
+    // adaptive extra rounds (pick_extra_rounds; the rule: schedule.h), X
+    // following the search two back
+    static constexpr int kCutSlots = ReadbackSlots::kSlots;
+    AdaptiveRounds adapt;
     int64_t adapt_seq = 0;   // grouped searches enqueued with a cuts slot
     // [kCutSlots][kMaxPipeline][2] per search and group: most cuts, fewest root empties
-    int32_t* cuts_dev = nullptr;
-    int32_t* cuts_host = nullptr;  // pinned copies
+    ReadbackSlots cuts;
     int cut_x[kCutSlots] = {-1, -1, -1, -1};  // X of the search in the slot (-1: slot empty)
     int cut_groups[kCutSlots] = {};
-    hipEvent_t cuts_ev[kCutSlots][kMaxPipeline] = {};
-    // allocated into locals and published only when every allocation
-    // succeeded (a failure leaves nothing half-initialised behind)
-    int ensure_cut_slots() {
-        if (cuts_dev) return OAMD_OK;
-        int32_t* dev = nullptr;
-        int32_t* host = nullptr;
-        hipEvent_t evs[kCutSlots][kMaxPipeline] = {};
-        int rc = dalloc(&dev, (size_t)2 * kCutSlots * kMaxPipeline);
-        if (!rc && hipHostMalloc((void**)&host, sizeof(int32_t) * 2 * kCutSlots * kMaxPipeline) != hipSuccess)
-            rc = fail(OAMD_RUNTIME, "cut slots: hipHostMalloc failed");
-        for (auto& row : evs)
-            for (auto& x : row)
-                if (!rc && hipEventCreateWithFlags(&x, readback_event_flags()) != hipSuccess)
-                    rc = fail(OAMD_RUNTIME, "cut slots: hipEventCreate failed");
-        if (rc) {
-            for (auto& row : evs)
-                for (auto x : row)
-                    if (x) (void)hipEventDestroy(x);
-            if (host) (void)hipHostFree(host);
-            dfree(dev);
-            return rc;
-        }
-        cuts_host = host;
-        std::memcpy(cuts_ev, evs, sizeof(evs));
-        cuts_dev = dev;
-        return OAMD_OK;
-    }
     // free-running self-play (oamd_engine_selfplay_steps, tree.hip k_tree_free):
     // games play their moves without waiting for each other; the host enqueues
     // rounds until every group's remaining-games counter (read back two chunks
@@ -266,35 +250,11 @@ struct oamd_engine {
     // base chunks wait for the chunk two back before they are enqueued
     // (OAMD_SPIN_SYNC=1: no wait, A/B only)
     bool throttle_enqueue = !spin_sync();
-    static constexpr int kFreeSlots = 4;
+    static constexpr int kFreeSlots = ReadbackSlots::kSlots;
     static constexpr int kFreeTailRounds = 4;
-    int32_t* remaining_dev = nullptr;   // [kMaxPipeline]
-    int32_t* remaining_host = nullptr;  // [kFreeSlots][kMaxPipeline], pinned
-    hipEvent_t free_ev[kFreeSlots][kMaxPipeline] = {};
-    int ensure_free_slots() {
-        if (remaining_dev) return OAMD_OK;
-        int32_t* dev = nullptr;
-        int32_t* host = nullptr;
-        hipEvent_t evs[kFreeSlots][kMaxPipeline] = {};
-        int rc = dalloc(&dev, (size_t)kMaxPipeline);
-        if (!rc && hipHostMalloc((void**)&host, sizeof(int32_t) * kFreeSlots * kMaxPipeline) != hipSuccess)
-            rc = fail(OAMD_RUNTIME, "free-running slots: hipHostMalloc failed");
-        for (auto& row : evs)
-            for (auto& x : row)
-                if (!rc && hipEventCreateWithFlags(&x, readback_event_flags()) != hipSuccess)
-                    rc = fail(OAMD_RUNTIME, "free-running slots: hipEventCreate failed");
-        if (rc) {
-            for (auto& row : evs)
-                for (auto x : row)
-                    if (x) (void)hipEventDestroy(x);
-            if (host) (void)hipHostFree(host);
-            dfree(dev);
-            return rc;
-        }
-        remaining_host = host;
-        std::memcpy(free_ev, evs, sizeof(evs));
-        remaining_dev = dev;
-        return OAMD_OK;
+    ReadbackSlots remaining;  // dev [kMaxPipeline], host [kFreeSlots][kMaxPipeline]
+    int ensure_remaining() {
+        return remaining.ensure((size_t)kMaxPipeline, (size_t)kFreeSlots * kMaxPipeline, "free-running slots");
     }
     // workgroups of an extra round's ResNet launch (0 = the regular grid)
     int extra_grid = 128;
@@ -305,18 +265,23 @@ struct oamd_engine {
     // rows are evaluated by consecutive launches on its stream
     int nn_batch = 0;
     int n_pipe_streams = 0;
-    int n_events = 0;  // sel_ev / nn_ev pairs created
+    int n_events = 0;  // sel_ev created
     hipStream_t pipe_stream[kMaxPipeline] = {};
     hipEvent_t fork_ev = nullptr;
     // NN tokens: the pipeline groups' ResNet launches form nn_chains chains
     // (group k in chain k % nn_chains); launches of one chain run one after
-    // another, chains run concurrently (1 = every launch serialised)
+    // another (a token event passed between the group streams), each owning
+    // every CU while the other groups' tree kernels run beside it; chains run
+    // concurrently (1 = every launch serialised). The default is one chain
+    // per group (2 groups, 2 chains): a group's launch starts as soon as its
+    // selection is done
     static constexpr int kMaxChains = 4;
     hipEvent_t nn_token[kMaxChains] = {};
     int nn_chains = 2;
-    hipStream_t nn_stream = nullptr;
+    // never used, but created ahead of the group / thread streams: without it the single-game thread split's
+    // 800-simulation search measured 10.0 instead of 5.1 ms (profiles/schedule_refactor/ab.json)
+    hipStream_t idle_stream = nullptr;
     hipEvent_t sel_ev[kMaxPipeline] = {};
-    hipEvent_t nn_ev[kMaxPipeline] = {};
     hipEvent_t join_ev[kMaxPipeline] = {};
     // timing: kEvPerBlock events per (step, group) of a search, in two pools used in
     // turn, so a search never waits for the previous one's events; a pool is
@@ -327,8 +292,6 @@ struct oamd_engine {
     std::vector<hipEvent_t> ev[2];
     int ev_blocks[2] = {0, 0};  // pending (round, group) blocks per pool
     int ev_final[2] = {0, 0};   // first block of the backup-only final round
-    int ev_K[2] = {1, 1};       // groups per round of those blocks
-    int ev_nn_groups[2] = {1, 1};  // groups (0 .. n-1) whose NN launches carry events
     int64_t ev_launches[2] = {0, 0};  // k_resnet launches inside those blocks
     int64_t ev_rows[2] = {0, 0};
     // NN busy time (oamd_engine_nn_busy): while timing is enabled, EVERY
@@ -375,7 +338,7 @@ struct oamd_engine {
             float ms = 0.0f;
             // blocks of different groups end on different streams; the final
             // round records no NN events
-            const bool nn = i < ev_final[p] && i % ev_K[p] < ev_nn_groups[p];
+            const bool nn = i < ev_final[p];
             HIPCHK(hipEventSynchronize(b[1]));
             if (nn) HIPCHK(hipEventSynchronize(b[3]));
             HIPCHK(hipEventElapsedTime(&ms, b[0], b[1]));
@@ -455,22 +418,24 @@ struct oamd_engine {
     }
 
     int L() const { return cfg.num_threads * cfg.batch_size; }
+    int steps() const { return search_steps(cfg.num_simulations, L()); }
     // thread-split schedule for one game (OAMD_TREE_SPLIT=0 in the environment: off)
-    static bool tree_split() {
+    bool thread_split() const {
         static const bool v = [] {
             const char* e = getenv("OAMD_TREE_SPLIT");
             return e ? atoi(e) != 0 : true;
         }();
-        return v;
+        return v && thread_split_shape(G, cfg.num_threads);
     }
-    // K group streams (2 in the single-game thread split) and their events; the
-    // thread split needs a select / NN event pair per virtual thread (nev >= K)
+    // K streams (one per pipeline group, or per virtual thread of the
+    // single-game thread split) and their events; the thread split also needs
+    // a select event per virtual thread (nev)
     int ensure_streams(int K, int nev) {
         if (K <= 1 && nev <= 1) return OAMD_OK;
         if (!fork_ev) HIPCHK(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
         for (int c = 0; c < kMaxChains; ++c)
             if (!nn_token[c]) HIPCHK(hipEventCreateWithFlags(&nn_token[c], hipEventDisableTiming));
-        if (!nn_stream) HIPCHK(hipStreamCreateWithFlags(&nn_stream, hipStreamNonBlocking));
+        if (!idle_stream) HIPCHK(hipStreamCreateWithFlags(&idle_stream, hipStreamNonBlocking));
         while (n_pipe_streams < K) {
             const int k = n_pipe_streams;
             HIPCHK(hipStreamCreateWithFlags(&pipe_stream[k], hipStreamNonBlocking));
@@ -483,7 +448,6 @@ struct oamd_engine {
             // operations): no system-scope fence (its host-visibility cache
             // maintenance) on the cross-stream path of every round
             HIPCHK(hipEventCreateWithFlags(&sel_ev[k], hipEventDisableTiming | hipEventDisableSystemFence));
-            HIPCHK(hipEventCreateWithFlags(&nn_ev[k], hipEventDisableTiming));
             ++n_events;
         }
         return OAMD_OK;
@@ -516,7 +480,7 @@ struct oamd_engine {
         E.counters = counters;
         E.rowlist = rowlist;
         E.tstate = tstate;
-        E.steps = (cfg.num_simulations + L() - 1) / L();
+        E.steps = steps();
         E.B = cfg.batch_size;
         E.terminal_skip = exact_interleaving ? 1 : 0;
         return E;
@@ -586,32 +550,17 @@ struct oamd_engine {
         for (auto& pool : ev)
             for (auto e : pool) (void)hipEventDestroy(e);
         for (auto& c : span_chunks) dfree(c.p);
-        if (cuts_dev) {
-            (void)hipDeviceSynchronize();  // no copy into cuts_host in flight
-            dfree(cuts_dev);
-            (void)hipHostFree(cuts_host);
-            for (auto& row : cuts_ev)
-                for (auto x : row) (void)hipEventDestroy(x);
-        }
-        if (remaining_dev) {
-            (void)hipDeviceSynchronize();  // no copy into remaining_host in flight
-            dfree(remaining_dev);
-            (void)hipHostFree(remaining_host);
-            for (auto& row : free_ev)
-                for (auto x : row) (void)hipEventDestroy(x);
-        }
+        cuts.destroy();
+        remaining.destroy();
         for (int k = 0; k < n_pipe_streams; ++k) {
             (void)hipStreamDestroy(pipe_stream[k]);
             (void)hipEventDestroy(join_ev[k]);
         }
-        for (int k = 0; k < n_events; ++k) {
-            (void)hipEventDestroy(sel_ev[k]);
-            (void)hipEventDestroy(nn_ev[k]);
-        }
+        for (int k = 0; k < n_events; ++k) (void)hipEventDestroy(sel_ev[k]);
         if (fork_ev) (void)hipEventDestroy(fork_ev);
         for (int c = 0; c < kMaxChains; ++c)
             if (nn_token[c]) (void)hipEventDestroy(nn_token[c]);
-        if (nn_stream) (void)hipStreamDestroy(nn_stream);
+        if (idle_stream) (void)hipStreamDestroy(idle_stream);
     }
 };
 
@@ -1046,8 +995,7 @@ int oamd_engine_reset(oamd_engine* e, int32_t game, uint64_t seed) {
 }
 
 int oamd_engine_search_begin(oamd_engine* e, int32_t* steps) {
-    const int L = e->L();
-    e->steps_left = (e->cfg.num_simulations + L - 1) / L;  // search_thread.cpp:50-52
+    e->steps_left = e->steps();
     e->steps_total = e->steps_left;
     e->step_phase = 0;
     if (steps) *steps = e->steps_left;
@@ -1154,10 +1102,12 @@ int oamd_engine_tree_timing(const oamd_engine* ce, float* select_ms, float* back
 // groups, each on its own stream, so one group's tree kernels (latency-bound,
 // a wave per game) run while another group's ResNet launch owns the MFMA
 // units. Games are independent, so the results are identical for every K.
-struct GroupPlan {
-    int K = 1;
+struct GroupPlan : GroupSplit {
     hipStream_t st[kMaxPipeline] = {};
-    int g0[kMaxPipeline] = {}, ng[kMaxPipeline] = {};
+    // ResNet launches of one round: the most of any group (a search's busy-time
+    // slots are [group][round][launch]) and over all groups; its rows
+    int max_launches = 1;
+    int64_t round_launches = 0, round_rows = 0;
 };
 
 static int native_search_checks(const oamd_engine* e, const oamd_net* net) {
@@ -1170,26 +1120,20 @@ static int native_search_checks(const oamd_engine* e, const oamd_net* net) {
 
 static GroupPlan plan_groups(oamd_engine* e) {
     GroupPlan P;
-    int K = e->pipeline > 0 ? e->pipeline : (e->G >= 64 ? 2 : 1);
-    if (K > e->G) K = e->G;
-    if (K > kMaxPipeline) K = kMaxPipeline;
-    P.K = K;
-    for (int k = 0; k < K; ++k) {
-        P.g0[k] = (int)((int64_t)e->G * k / K);
-        P.ng[k] = (int)((int64_t)e->G * (k + 1) / K) - P.g0[k];
-        P.st[k] = K == 1 ? e->stream : e->pipe_stream[k];
+    static_cast<GroupSplit&>(P) = split_groups(e->G, e->pipeline);
+    for (int k = 0; k < P.K; ++k) {
+        P.st[k] = P.K == 1 ? e->stream : e->pipe_stream[k];
+        const int n = group_launches(P.ng[k], e->L(), e->nn_batch);
+        P.max_launches = std::max(P.max_launches, n);
+        P.round_launches += n;
+        P.round_rows += (int64_t)P.ng[k] * e->L();
     }
     return P;
 }
 
-// Extra rounds of a native grouped search (chain splitting, k_tree): the
-// reference's interleaving only
+// The most extra rounds of a native grouped search (chain splitting, k_tree)
 static int extra_rounds(const oamd_engine* e) {
-    if (!e->exact_interleaving || e->chain_budget <= 0) return 0;
-    // a cut follows >= budget all-terminal batches of its round, and a search
-    // has T x steps batches per game: no game can use more cuts than that
-    const int64_t batches = (int64_t)e->cfg.num_threads * ((e->cfg.num_simulations + e->L() - 1) / e->L());
-    return (int)std::min<int64_t>(e->chain_cuts, batches / e->chain_budget);
+    return extra_round_cap(e->exact_interleaving, e->chain_budget, e->chain_cuts, e->cfg.num_threads, e->steps());
 }
 
 // Extra rounds X of the next grouped search. Fixed: chain_cuts. Adaptive: a
@@ -1200,56 +1144,29 @@ static int extra_rounds(const oamd_engine* e) {
 // (done by now: the previous one is still queued, so the read-back does not
 // drain the queue): its most cuts and the fewest empty squares of its roots.
 static int pick_extra_rounds(oamd_engine* e, int* X) {
-    *X = extra_rounds(e);
-    if (*X == 0 || !e->adapt_on) return OAMD_OK;
-    if (int rc = e->ensure_cut_slots()) return rc;
+    const int cap = extra_rounds(e);
+    *X = cap;
+    if (cap == 0 || !e->adapt.on) return OAMD_OK;
+    if (int rc = e->cuts.ensure((size_t)2 * oamd_engine::kCutSlots * kMaxPipeline,
+                                (size_t)2 * oamd_engine::kCutSlots * kMaxPipeline, "cut slots"))
+        return rc;
     const int64_t q = e->adapt_seq - 2;
     const int s = q >= 0 ? (int)(q % oamd_engine::kCutSlots) : 0;
     if (q >= 0 && e->cut_x[s] >= 0) {
         int used = 0, empties = 64;
         for (int k = 0; k < e->cut_groups[s]; ++k) {
-            HIPCHK(host_wait(e->cuts_ev[s][k]));
-            used = std::max(used, (int)e->cuts_host[2 * (s * kMaxPipeline + k)]);
-            empties = std::min(empties, (int)e->cuts_host[2 * (s * kMaxPipeline + k) + 1]);
+            HIPCHK(host_wait(e->cuts.ev[s][k]));
+            used = std::max(used, (int)e->cuts.host[2 * (s * kMaxPipeline + k)]);
+            empties = std::min(empties, (int)e->cuts.host[2 * (s * kMaxPipeline + k) + 1]);
         }
-        // the cuts come with the endgame: outside it no chain outlasts the
-        // budget (used = 0), within ~9 empty squares of the end a game's whole
-        // search can be all terminal (used = 12 of 50 batches per thread at
-        // budget 4; profiles/r04/ab/adaptive_demand_log.txt). The root loses
-        // one empty square per move, so the fewest empties two searches back
-        // announce the endgame before it starts; a search that needed cuts
-        // raises the threshold past its root. Outside the endgame X = the
-        // cuts used + the minimum, or 2X + 2 when a game ran out of cuts
-        // (k_tree reports X + 1: X = 0 still counts the chains that would
-        // have been split)
-        // the raised threshold decays by one per search without cuts back to
-        // kEndgameEmpties (a mid-game chain must not pin the full
-        // count for the engine's lifetime)
-        if (used > 0) e->adapt_empties = std::max(e->adapt_empties, empties + 3);
-        else if (e->adapt_empties > oamd_engine::kEndgameEmpties) --e->adapt_empties;
-        if (empties <= e->adapt_empties) e->adapt_x = e->chain_cuts;
-        else e->adapt_x = (used > e->cut_x[s] ? 2 * e->cut_x[s] + 2 : used) + e->adapt_min;
+        e->adapt.observe(e->cut_x[s], used, empties, e->chain_cuts);
         static const bool plog = getenv("OAMD_ADAPT_LOG") != nullptr;
         if (plog)
             fprintf(stderr, "adapt search %lld X %d used %d empties %d\n", (long long)q, e->cut_x[s], used, empties);
         e->cut_x[s] = -1;
     }
-    // the first two searches (nothing read back yet) run the minimum: games
-    // usually start from an opening, and a game that needs more cuts only
-    // runs a longer round
-    *X = e->adapt_x >= 0 ? std::clamp(e->adapt_x, std::min(e->adapt_min, *X), *X) : std::min(e->adapt_min, *X);
+    *X = e->adapt.pick(cap);
     return OAMD_OK;
-}
-
-// ResNet launches per group and round (the most of any group: nn_batch splits
-// a group's rows into consecutive launches)
-static int launches_per_group_round(const oamd_engine* e, const GroupPlan& P) {
-    int n = 1;
-    for (int k = 0; k < P.K; ++k) {
-        const int grows = P.ng[k] * e->L(), cb = e->nn_batch > 0 ? e->nn_batch : grows;
-        n = std::max(n, (grows + cb - 1) / cb);
-    }
-    return n;
 }
 
 // Sampled timing of one search: claim the current event pool (every
@@ -1269,58 +1186,55 @@ static int timing_begin(oamd_engine* e, int steps, int NB, bool* timed) {
     return OAMD_OK;
 }
 
-static void timing_end(oamd_engine* e, int steps, int NB, bool split, const GroupPlan& P) {
+// Hand the claimed pool's recorded blocks over: `blocks` of them, NB per
+// round; those from first_final on (a search's backup-only final round; none
+// in a free-running chunk) carry no NN events, every round before has
+// round_launches ResNet launches of round_rows rows in all.
+static void timing_end(oamd_engine* e, int blocks, int first_final, int NB, int64_t round_launches,
+                       int64_t round_rows) {
     const int pool = e->ev_cur;
-    e->ev_blocks[pool] = (steps + 1) * NB;
-    e->ev_final[pool] = steps * NB;
-    e->ev_K[pool] = NB;
-    e->ev_nn_groups[pool] = NB;
-    int64_t nl = 0, rows = 0;
-    if (split) {
-        nl = e->cfg.num_threads;
-        rows = e->L();
-    }
-    for (int k = 0; !split && k < e->ev_nn_groups[pool]; ++k) {
-        const int grows = P.ng[k] * e->L(), cb = e->nn_batch > 0 ? e->nn_batch : grows;
-        nl += (grows + cb - 1) / cb;
-        rows += grows;
-    }
-    e->ev_launches[pool] = (int64_t)steps * nl;
-    e->ev_rows[pool] = (int64_t)steps * rows;
+    e->ev_blocks[pool] = blocks;
+    e->ev_final[pool] = first_final;
+    e->ev_launches[pool] = first_final / NB * round_launches;
+    e->ev_rows[pool] = first_final / NB * round_rows;
     e->ev_cur ^= 1;
 }
+// a grouped search of `rounds` NN rounds (steps + extra rounds) and its final round
+static void timing_end_search(oamd_engine* e, int rounds, const GroupPlan& P) {
+    timing_end(e, (rounds + 1) * P.K, rounds * P.K, P.K, P.round_launches, P.round_rows);
+}
 
-// Timing of R free-running rounds (every round has NN launches, none is a
-// backup-only final round)
-static void timing_end_rounds(oamd_engine* e, int R, const GroupPlan& P) {
-    const int pool = e->ev_cur;
-    e->ev_blocks[pool] = R * P.K;
-    e->ev_final[pool] = R * P.K;
-    e->ev_K[pool] = P.K;
-    e->ev_nn_groups[pool] = P.K;
-    int64_t nl = 0, rows = 0;
-    for (int k = 0; k < P.K; ++k) {
-        const int grows = P.ng[k] * e->L(), cb = e->nn_batch > 0 ? e->nn_batch : grows;
-        nl += (grows + cb - 1) / cb;
-        rows += grows;
-    }
-    e->ev_launches[pool] = (int64_t)R * nl;
-    e->ev_rows[pool] = (int64_t)R * rows;
-    e->ev_cur ^= 1;
+// The NN half of one (round, group) block, on group k's stream after its tree
+// launch: the evaluation list `count` rows long at most, in launches of
+// nn_batch rows, one after another within the group's NN chain (the token).
+// ev: the block's timing events or nullptr; span: the block's busy-time slots
+// or nullptr; max_wgs: the ResNet grid (0 = the regular one).
+static int enqueue_group_nn(oamd_engine* e, const EngineView& E, const NetView& N, const GroupPlan& P, int k,
+                            bool wait_token, hipEvent_t* ev, int* count, unsigned long long* span, int max_wgs) {
+    hipStream_t sk = P.st[k];
+    hipEvent_t token = e->nn_token[k % std::min(e->nn_chains, P.K)];
+    if (P.K > 1 && wait_token) HIPCHK(hipStreamWaitEvent(sk, token, 0));
+    if (ev) HIPCHK(hipEventRecord(ev[2], sk));
+    const int grows = P.ng[k] * E.L, cb = launch_rows(grows, e->nn_batch);
+    const size_t r0 = (size_t)P.g0[k] * E.L;
+    for (int r = 0, j = 0; r < grows; r += cb, ++j)
+        launch_resnet_packed(N, E.feat, E.FW, E.H, std::min(cb, grows - r), E.policy, E.value, sk, E.rowlist + r0 + r,
+                             count, r, span ? span + (size_t)2 * j : nullptr, max_wgs);
+    if (ev) HIPCHK(hipEventRecord(ev[3], sk));
+    if (P.K > 1) HIPCHK(hipEventRecord(token, sk));
+    return OAMD_OK;
 }
 
 // The rounds of one native search over the groups of P, enqueued on the group
 // streams (already forked from the engine stream). chained: the groups'
 // streams carry on from a previous search of the same call (a multi-move
 // self-play call), so its first NN launch also waits for the NN token.
-
 static int enqueue_group_rounds(oamd_engine* e, const NetView& N, const GroupPlan& P, int steps, int X, bool timed,
                                 bool chained) {
     const EngineView E = e->view();
-    const int K = P.K, L = e->L();
+    const int K = P.K;
     const int T = e->cfg.num_threads, B = e->cfg.batch_size;
     const int pool = e->ev_cur;
-    const int nch = e->nn_chains < K ? e->nn_chains : K;
     // chain splitting (k_tree): X extra rounds (pick_extra_rounds) absorb the
     // rounds a split chain delays its game by; only the reference's
     // interleaving has chains
@@ -1330,7 +1244,7 @@ static int enqueue_group_rounds(oamd_engine* e, const NetView& N, const GroupPla
     const int budget = splitting ? e->chain_budget : 0;
     const int S = steps + X;
     // adaptive X: each group's most cuts, into this search's slot
-    const bool adapt = splitting && e->adapt_on;
+    const bool adapt = splitting && e->adapt.on;
     const int cs = (int)(e->adapt_seq % oamd_engine::kCutSlots);
     ++e->grouped_searches;
     e->grouped_rounds += S;
@@ -1345,12 +1259,11 @@ static int enqueue_group_rounds(oamd_engine* e, const NetView& N, const GroupPla
     // records events for every round, the extra ones included, and counts the
     // NN rows of every round (counters [4..5]): launches, rows and busy time
     // of a timed search cover the same launches (steps + X)
-    const int nlg = launches_per_group_round(e, P);
+    const int nlg = P.max_launches;
     unsigned long long* span = nullptr;  // this search's busy-time slots (timing on)
     if (int rc = e->reserve_spans((int64_t)K * S * nlg, &span)) return rc;
     for (int s = 0; s <= S; ++s) {
         for (int k = 0; k < K; ++k) {
-            const size_t r0 = (size_t)P.g0[k] * L;
             hipStream_t sk = P.st[k];
             hipEvent_t* ev = timed ? &e->ev[pool][kEvPerBlock * (s * K + k)] : nullptr;
             if (ev) HIPCHK(hipEventRecord(ev[0], sk));
@@ -1358,110 +1271,76 @@ static int enqueue_group_rounds(oamd_engine* e, const NetView& N, const GroupPla
             // the other one (which round s-1's launch, done by now, read); the
             // final round zeroes counter 0 for the next search's round 0
             int* cnt = e->rowcount + 2 * k;
-            int* cuts = adapt ? e->cuts_dev + 2 * (cs * kMaxPipeline + k) : nullptr;
+            int* cuts = adapt ? e->cuts.dev + 2 * (cs * kMaxPipeline + k) : nullptr;
             launch_tree(E, sk, s > 0, s < S, T, B, P.g0[k], P.ng[k], 0, -1, s < S ? cnt + (s & 1) : nullptr,
                         s < S ? cnt + ((s + 1) & 1) : cnt, s == 0, budget, X, timed,
                         s == 0 || s == S ? cuts : nullptr);
             if (ev) HIPCHK(hipEventRecord(ev[1], sk));
             if (s == S) {
                 if (adapt) {
-                    HIPCHK(hipMemcpyAsync(e->cuts_host + 2 * (cs * kMaxPipeline + k), cuts, 2 * sizeof(int32_t),
+                    HIPCHK(hipMemcpyAsync(e->cuts.host + 2 * (cs * kMaxPipeline + k), cuts, 2 * sizeof(int32_t),
                                           hipMemcpyDeviceToHost, sk));
-                    HIPCHK(hipEventRecord(e->cuts_ev[cs][k], sk));
+                    HIPCHK(hipEventRecord(e->cuts.ev[cs][k], sk));
                 }
                 continue;
             }
-            // the groups' NN launches run one after another (OAMD_NN_ORDER)
-            hipStream_t ns = sk;
-            if (K > 1 && OAMD_NN_ORDER == 2) {
-                ns = e->nn_stream;
-                HIPCHK(hipEventRecord(e->sel_ev[k], sk));
-                HIPCHK(hipStreamWaitEvent(ns, e->sel_ev[k], 0));
-            } else if (K > 1 && OAMD_NN_ORDER == 1 && (s > 0 || k >= nch || chained)) {
-                HIPCHK(hipStreamWaitEvent(sk, e->nn_token[k % nch], 0));
-            }
-            if (ev) HIPCHK(hipEventRecord(ev[2], ns));
-            const int grows = P.ng[k] * L;
-            const int cb = e->nn_batch > 0 ? e->nn_batch : grows;
-            // the extra rounds evaluate lagging games only: a small looping grid
-            const int max_wgs = s >= steps ? e->extra_grid : 0;
-            for (int r = 0, j = 0; r < grows; r += cb, ++j)
-                launch_resnet_packed(N, E.feat, E.FW, E.H, std::min(cb, grows - r), E.policy, E.value, ns,
-                                     E.rowlist + r0 + r, cnt + (s & 1), r,
-                                     span ? span + (size_t)2 * ((k * S + s) * nlg + j) : nullptr, max_wgs);
-            if (ev) HIPCHK(hipEventRecord(ev[3], ns));
-            if (K > 1 && OAMD_NN_ORDER == 2) {
-                HIPCHK(hipEventRecord(e->nn_ev[k], ns));
-                HIPCHK(hipStreamWaitEvent(sk, e->nn_ev[k], 0));
-            } else if (K > 1 && OAMD_NN_ORDER == 1) {
-                HIPCHK(hipEventRecord(e->nn_token[k % nch], sk));
-            }
+            // a chain's first launch of a call has no token to wait for; the
+            // extra rounds evaluate lagging games only: a small looping grid
+            const bool first = s == 0 && k < std::min(e->nn_chains, K) && !chained;
+            if (int rc = enqueue_group_nn(e, E, N, P, k, !first, ev, cnt + (s & 1),
+                                          span ? span + (size_t)2 * ((k * S + s) * nlg) : nullptr,
+                                          s >= steps ? e->extra_grid : 0))
+                return rc;
         }
     }
     return OAMD_OK;
 }
 
-static int fork_groups(oamd_engine* e, const GroupPlan& P) {
-    if (P.K > 1) {  // fork from the caller's stream
+// n > 1 group or thread streams fork from the caller's stream ...
+static int fork_streams(oamd_engine* e, const hipStream_t* st, int n) {
+    if (n > 1) {
         HIPCHK(hipEventRecord(e->fork_ev, e->stream));
-        for (int k = 0; k < P.K; ++k) HIPCHK(hipStreamWaitEvent(P.st[k], e->fork_ev, 0));
+        for (int k = 0; k < n; ++k) HIPCHK(hipStreamWaitEvent(st[k], e->fork_ev, 0));
     }
     return OAMD_OK;
 }
-
-static int join_groups(oamd_engine* e, const GroupPlan& P) {
-    if (P.K > 1) {  // join back into the caller's stream
-        for (int k = 0; k < P.K; ++k) {
-            HIPCHK(hipEventRecord(e->join_ev[k], P.st[k]));
-            HIPCHK(hipStreamWaitEvent(e->stream, e->join_ev[k], 0));
-        }
+// ... and join back into it
+static int join_streams(oamd_engine* e, const hipStream_t* st, int n) {
+    for (int k = 0; n > 1 && k < n; ++k) {
+        HIPCHK(hipEventRecord(e->join_ev[k], st[k]));
+        HIPCHK(hipStreamWaitEvent(e->stream, e->join_ev[k], 0));
     }
     return OAMD_OK;
 }
+static int fork_groups(oamd_engine* e, const GroupPlan& P) { return fork_streams(e, P.st, P.K); }
+static int join_groups(oamd_engine* e, const GroupPlan& P) { return join_streams(e, P.st, P.K); }
 
-int oamd_engine_search(oamd_engine* e, oamd_net* net, int64_t* sims, int64_t* evals) {
-    if (int rc = native_search_checks(e, net)) return rc;
-    DeviceGuard dg(e->device);
-    const int L = e->L();
-    const int steps = (e->cfg.num_simulations + L - 1) / L;
+// One game with T > 1 virtual threads (the drop-in MCTS, latency mode):
+// virtual thread t's tree operations (backup of its batch s-1 + selection
+// of batch s) and its ResNet launches alternate on a stream of its own, so
+// thread t's rows are evaluated while the tree kernel backs up and selects
+// for thread t+1 (the overlap the reference gets from its T threads,
+// search_thread.cpp:59-128). The tree operations keep the order of one
+// launch per round (thread 0 .. T-1, round by round) through an event
+// from each to the next, so results are identical; an operation waits
+// across streams only for the previous thread's tree operation, which ends
+// while this thread's ResNet launch still runs (a ResNet launch waiting
+// across streams for its selection, and a selection for its thread's
+// launch, each cost ~13 us of queue latency per round).
+static int search_thread_split(oamd_engine* e, const NetView& N) {
     const EngineView E = e->view();
-    const NetView N = net->view();
-    GroupPlan P = plan_groups(e);
-    const int K = P.K;
+    const int steps = e->steps();
     const int T = e->cfg.num_threads, B = e->cfg.batch_size;
-    // One game with T > 1 virtual threads (the drop-in MCTS, latency mode):
-    // virtual thread t's tree operations (backup of its batch s-1 + selection
-    // of batch s) and its ResNet launches alternate on a stream of its own, so
-    // thread t's rows are evaluated while the tree kernel backs up and selects
-    // for thread t+1 (the overlap the reference gets from its T threads,
-    // search_thread.cpp:59-128). The tree operations keep the order of one
-    // launch per round (thread 0 .. T-1, round by round) through an event
-    // from each to the next, so results are identical; an operation waits
-    // across streams only for the previous thread's tree operation, which ends
-    // while this thread's ResNet launch still runs (a ResNet launch waiting
-    // across streams for its selection, and a selection for its thread's
-    // launch, each cost ~13 us of queue latency per round).
-    const bool split = e->G == 1 && K == 1 && T > 1 && T <= kMaxPipeline && e->tree_split();
-    const int NB = split ? T : K;  // timing blocks per round
-    int rc = split ? e->ensure_streams(T, T) : e->ensure_streams(K, K);
-    if (rc) return rc;
-    if (!split) P = plan_groups(e);  // the group streams exist now
-    if (sims || evals) HIPCHK(hipMemsetAsync(e->counters, 0, 2 * sizeof(unsigned long long), e->stream));
-    // sampled timing: per (round, group) kEvPerBlock events: tree begin/end, NN
-    // begin/end (on the NN stream, after its waits; not in the final round)
+    if (int rc = e->ensure_streams(T, T)) return rc;
+    // sampled timing: per (round, thread) kEvPerBlock events: tree begin/end,
+    // NN begin/end (not in the final round)
     bool timed = false;
-    int X = 0;
-    if (!split && (rc = pick_extra_rounds(e, &X))) return rc;
-    const int rounds = steps + X;  // NN rounds
-    if ((rc = timing_begin(e, rounds, NB, &timed))) return rc;
+    if (int rc = timing_begin(e, steps, T, &timed)) return rc;
     const int pool = e->ev_cur;
-    unsigned long long* span = nullptr;  // busy-time slots [thread][round] of the split schedule
-    if (split && (rc = e->reserve_spans((int64_t)T * steps, &span))) return rc;
-    if (split) {  // every thread stream after the caller's stream
-        HIPCHK(hipEventRecord(e->fork_ev, e->stream));
-        for (int t = 0; t < T; ++t) HIPCHK(hipStreamWaitEvent(e->pipe_stream[t], e->fork_ev, 0));
-    }
-    for (int s = 0; split && s <= steps; ++s) {
+    unsigned long long* span = nullptr;  // busy-time slots [thread][round]
+    if (int rc = e->reserve_spans((int64_t)T * steps, &span)) return rc;
+    if (int rc = fork_streams(e, e->pipe_stream, T)) return rc;
+    for (int s = 0; s <= steps; ++s) {
         for (int t = 0; t < T; ++t) {
             hipEvent_t* ev = timed ? &e->ev[pool][kEvPerBlock * (s * T + t)] : nullptr;
             hipStream_t ts = e->pipe_stream[t];  // after this thread's batch s-1 evaluation (stream order)
@@ -1479,19 +1358,39 @@ int oamd_engine_search(oamd_engine* e, oamd_net* net, int64_t* sims, int64_t* ev
             if (ev) HIPCHK(hipEventRecord(ev[3], ts));
         }
     }
-    if (split) {  // the caller's stream after every thread stream
-        for (int t = 0; t < T; ++t) {
-            HIPCHK(hipEventRecord(e->join_ev[t], e->pipe_stream[t]));
-            HIPCHK(hipStreamWaitEvent(e->stream, e->join_ev[t], 0));
-        }
-    }
-    if (!split) {
-        if ((rc = fork_groups(e, P))) return rc;
-        if ((rc = enqueue_group_rounds(e, N, P, steps, X, timed, false))) return rc;
-    }
+    if (int rc = join_streams(e, e->pipe_stream, T)) return rc;
     LAUNCHCHK();
-    if (!split && (rc = join_groups(e, P))) return rc;
-    if (timed) timing_end(e, rounds, NB, split, P);
+    if (timed) timing_end(e, (steps + 1) * T, steps * T, T, T, e->L());
+    return OAMD_OK;
+}
+
+// The lock-step grouped search: every group's rounds between a fork from and
+// a join into the caller's stream
+static int search_grouped(oamd_engine* e, const NetView& N) {
+    const int K = plan_groups(e).K;
+    if (int rc = e->ensure_streams(K, K)) return rc;
+    const GroupPlan P = plan_groups(e);  // the group streams exist now
+    // sampled timing: per (round, group) kEvPerBlock events: tree begin/end, NN
+    // begin/end (after its waits; not in the final round)
+    bool timed = false;
+    int X = 0;
+    if (int rc = pick_extra_rounds(e, &X)) return rc;
+    const int steps = e->steps();
+    if (int rc = timing_begin(e, steps + X, K, &timed)) return rc;
+    if (int rc = fork_groups(e, P)) return rc;
+    if (int rc = enqueue_group_rounds(e, N, P, steps, X, timed, false)) return rc;
+    LAUNCHCHK();
+    if (int rc = join_groups(e, P)) return rc;
+    if (timed) timing_end_search(e, steps + X, P);
+    return OAMD_OK;
+}
+
+int oamd_engine_search(oamd_engine* e, oamd_net* net, int64_t* sims, int64_t* evals) {
+    if (int rc = native_search_checks(e, net)) return rc;
+    DeviceGuard dg(e->device);
+    if (sims || evals) HIPCHK(hipMemsetAsync(e->counters, 0, 2 * sizeof(unsigned long long), e->stream));
+    const NetView N = net->view();
+    if (int rc = e->thread_split() ? search_thread_split(e, N) : search_grouped(e, N)) return rc;
     // without counters requested the search is left in flight (stream order)
     if (sims || evals) {
         unsigned long long c[2] = {0, 0};
@@ -1577,10 +1476,7 @@ int oamd_engine_set_chain_split(oamd_engine* e, int32_t budget, int32_t cuts) {
 
 int oamd_engine_set_adaptive_extra_rounds(oamd_engine* e, int32_t enable, int32_t min_rounds) {
     if (min_rounds < 0 || min_rounds > 64) return fail(OAMD_INVALID_ARGUMENT, "adaptive extra rounds: min in [0, 64]");
-    e->adapt_on = enable != 0;
-    e->adapt_min = min_rounds;
-    e->adapt_x = -1;  // the next two searches run the minimum
-    e->adapt_empties = oamd_engine::kEndgameEmpties;
+    e->adapt.reset(enable != 0, min_rounds);  // the next two searches run the minimum
     for (int& x : e->cut_x) x = -1;
     return OAMD_OK;
 }
@@ -1699,15 +1595,28 @@ int oamd_engine_apply_actions(oamd_engine* e, const int32_t* actions_dev) {
     return OAMD_OK;
 }
 
-int oamd_engine_selfplay_move(oamd_engine* e, const oamd_selfplay_config* cfg, int32_t* actions_dev,
-                              int32_t* finished_dev, float* features_dev, float* policy_dev) {
-    if (cfg->temperature_moves < 0 || !(cfg->temperature > 0.0f) || cfg->opening_moves < 0)
-        return fail(OAMD_INVALID_ARGUMENT, "bad self-play config");
+// the move-choice part of a self-play config (all of it the arena uses)
+static bool move_cfg_ok(const oamd_selfplay_config* cfg) {
+    return cfg->temperature_moves >= 0 && cfg->temperature > 0.0f;
+}
+
+static int selfplay_cfg_checks(const oamd_selfplay_config* cfg, const float* features_dev, const float* policy_dev) {
+    if (!move_cfg_ok(cfg) || cfg->opening_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "bad self-play config");
     if (cfg->emit_targets && (!features_dev || !policy_dev))
         return fail(OAMD_INVALID_ARGUMENT, "emit_targets needs features and policy buffers");
-    SelfplayParams sp{cfg->temperature_moves, cfg->temperature, cfg->opening_moves, cfg->emit_targets};
+    return OAMD_OK;
+}
+
+static SelfplayParams selfplay_params(const oamd_selfplay_config* cfg) {
+    return SelfplayParams{cfg->temperature_moves, cfg->temperature, cfg->opening_moves, cfg->emit_targets};
+}
+
+int oamd_engine_selfplay_move(oamd_engine* e, const oamd_selfplay_config* cfg, int32_t* actions_dev,
+                              int32_t* finished_dev, float* features_dev, float* policy_dev) {
+    if (int rc = selfplay_cfg_checks(cfg, features_dev, policy_dev)) return rc;
     DeviceGuard dg(e->device);
-    launch_selfplay_move(e->view(), sp, 0, e->G, actions_dev, finished_dev, features_dev, policy_dev, e->stream);
+    launch_selfplay_move(e->view(), selfplay_params(cfg), 0, e->G, actions_dev, finished_dev, features_dev, policy_dev,
+                         e->stream);
     LAUNCHCHK();
     return OAMD_OK;
 }
@@ -1725,17 +1634,16 @@ int oamd_engine_selfplay_move(oamd_engine* e, const oamd_selfplay_config* cfg, i
 // lagging games have rows then. Returns once the last chunk is enqueued.
 static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg, int n_moves,
                                int per_move, int32_t* actions, int32_t* finished, float* feat, float* pol) {
-    if (int rc = e->ensure_free_slots()) return rc;
-    GroupPlan P = plan_groups(e);
-    const int K = P.K, L = e->L();
+    if (int rc = e->ensure_remaining()) return rc;
+    const GroupPlan P = plan_groups(e);
+    const int K = P.K;
     const int T = e->cfg.num_threads, B = e->cfg.batch_size;
-    const int steps = (e->cfg.num_simulations + L - 1) / L;
+    const int steps = e->steps();
     const EngineView E = e->view();
     const NetView N = net->view();
-    const SelfplayParams sp{cfg->temperature_moves, cfg->temperature, cfg->opening_moves, cfg->emit_targets};
+    const SelfplayParams sp = selfplay_params(cfg);
     const int budget = e->exact_interleaving && e->chain_budget > 0 ? e->chain_budget : 0;
-    const int nch = e->nn_chains < K ? e->nn_chains : K;
-    const int nlg = launches_per_group_round(e, P);
+    const int nlg = P.max_launches;
     if (int rc = fork_groups(e, P)) return rc;
     int64_t round = 0;
     // everything between the fork and the join; on an error the groups are
@@ -1744,8 +1652,8 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const oamd_selfpla
     auto rounds = [&]() -> int {
         for (int k = 0; k < K; ++k) {
             HIPCHK(hipMemsetAsync(e->rowcount + 2 * k, 0, 2 * sizeof(int32_t), P.st[k]));
-            HIPCHK(hipMemsetAsync(e->remaining_dev + k, 0, sizeof(int32_t), P.st[k]));
-            launch_free_begin(E, P.g0[k], P.ng[k], n_moves, e->remaining_dev + k, actions, finished, per_move, P.st[k]);
+            HIPCHK(hipMemsetAsync(e->remaining.dev + k, 0, sizeof(int32_t), P.st[k]));
+            launch_free_begin(E, P.g0[k], P.ng[k], n_moves, e->remaining.dev + k, actions, finished, per_move, P.st[k]);
         }
         bool gdone[kMaxPipeline] = {};
         const int64_t base_rounds = n_moves > 0 ? (int64_t)n_moves * steps + 1 : 0;
@@ -1764,15 +1672,15 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const oamd_selfpla
                 // (host budget)
                 if (chunk >= 2 && e->throttle_enqueue) {
                     const int slot = (int)((chunk - 2) % oamd_engine::kFreeSlots);
-                    for (int k = 0; k < K; ++k) HIPCHK(host_wait(e->free_ev[slot][k]));
+                    for (int k = 0; k < K; ++k) HIPCHK(host_wait(e->remaining.ev[slot][k]));
                 }
             } else {
                 if (chunk >= 2) {  // chunk - 2's readback: done by now while chunk - 1 is queued
                     const int slot = (int)((chunk - 2) % oamd_engine::kFreeSlots);
                     for (int k = 0; k < K; ++k) {
                         if (gdone[k]) continue;
-                        HIPCHK(host_wait(e->free_ev[slot][k]));
-                        if (e->remaining_host[slot * kMaxPipeline + k] == 0) gdone[k] = true;
+                        HIPCHK(host_wait(e->remaining.ev[slot][k]));
+                        if (e->remaining.host[slot * kMaxPipeline + k] == 0) gdone[k] = true;
                     }
                 }
                 bool all = true;
@@ -1797,30 +1705,24 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const oamd_selfpla
                     int* cnt = e->rowcount + 2 * k;
                     if (ev) HIPCHK(hipEventRecord(ev[0], sk));
                     launch_tree_free(E, sk, P.g0[k], P.ng[k], B, cnt + (r & 1), cnt + ((r + 1) & 1), budget, timed, sp,
-                                     n_moves, per_move, actions, finished, feat, pol, e->remaining_dev + k);
+                                     n_moves, per_move, actions, finished, feat, pol, e->remaining.dev + k);
                     if (ev) HIPCHK(hipEventRecord(ev[1], sk));
-                    if (K > 1 && (r > 0 || k >= nch)) HIPCHK(hipStreamWaitEvent(sk, e->nn_token[k % nch], 0));
-                    if (ev) HIPCHK(hipEventRecord(ev[2], sk));
-                    const int grows = P.ng[k] * L;
-                    const int cb = e->nn_batch > 0 ? e->nn_batch : grows;
-                    const size_t r0 = (size_t)P.g0[k] * L;
-                    for (int rr = 0, j = 0; rr < grows; rr += cb, ++j)
-                        launch_resnet_packed(N, E.feat, E.FW, E.H, std::min(cb, grows - rr), E.policy, E.value, sk,
-                                             E.rowlist + r0 + rr, cnt + (r & 1), rr,
-                                             span ? span + (size_t)2 * ((k * R + s) * nlg + j) : nullptr,
-                                             tail ? e->extra_grid : 0);
-                    if (ev) HIPCHK(hipEventRecord(ev[3], sk));
-                    if (K > 1) HIPCHK(hipEventRecord(e->nn_token[k % nch], sk));
+                    // a chain's first launch of the call has no token to wait for
+                    const bool first = r == 0 && k < std::min(e->nn_chains, K);
+                    if (int rc = enqueue_group_nn(e, E, N, P, k, !first, ev, cnt + (r & 1),
+                                                  span ? span + (size_t)2 * ((k * R + s) * nlg) : nullptr,
+                                                  tail ? e->extra_grid : 0))
+                        return rc;
                 }
             }
             const int slot = (int)(chunk % oamd_engine::kFreeSlots);
             for (int k = 0; k < K; ++k) {
                 if (gdone[k]) continue;
-                HIPCHK(hipMemcpyAsync(e->remaining_host + slot * kMaxPipeline + k, e->remaining_dev + k, sizeof(int32_t),
+                HIPCHK(hipMemcpyAsync(e->remaining.host + slot * kMaxPipeline + k, e->remaining.dev + k, sizeof(int32_t),
                                       hipMemcpyDeviceToHost, P.st[k]));
-                HIPCHK(hipEventRecord(e->free_ev[slot][k], P.st[k]));
+                HIPCHK(hipEventRecord(e->remaining.ev[slot][k], P.st[k]));
             }
-            if (timed) timing_end_rounds(e, R, P);
+            if (timed) timing_end(e, R * K, R * K, K, P.round_launches, P.round_rows);
             round += R;
         }
         // the next search (or call) starts with empty evaluation lists
@@ -1847,18 +1749,14 @@ int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfpla
                                int32_t per_move_outputs, int32_t* actions_dev, int32_t* finished_dev,
                                float* features_dev, float* policy_dev) {
     if (n_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "n_moves must be >= 0");
-    if (cfg->temperature_moves < 0 || !(cfg->temperature > 0.0f) || cfg->opening_moves < 0)
-        return fail(OAMD_INVALID_ARGUMENT, "bad self-play config");
-    if (cfg->emit_targets && (!features_dev || !policy_dev))
-        return fail(OAMD_INVALID_ARGUMENT, "emit_targets needs features and policy buffers");
+    if (int rc = selfplay_cfg_checks(cfg, features_dev, policy_dev)) return rc;
     if (int rc = native_search_checks(e, net)) return rc;
     DeviceGuard dg(e->device);
     const int G = e->G, C = 1 + 2 * e->cfg.history_size;
     // move i's outputs: the i-th slice of per-move buffers, or the same G-game buffers every move
     auto out = [&](int i, auto* p, int64_t per_game) { return p ? p + (per_move_outputs ? (int64_t)i * G * per_game : 0) : p; };
     GroupPlan P = plan_groups(e);
-    const int T = e->cfg.num_threads;
-    const bool split = G == 1 && P.K == 1 && T > 1 && T <= kMaxPipeline && e->tree_split();
+    const bool split = e->thread_split();
     if (!split && e->free_running) {
         if (int rc = e->ensure_streams(P.K, P.K)) return rc;
         return selfplay_steps_free(e, net, cfg, n_moves, per_move_outputs, actions_dev, finished_dev, features_dev,
@@ -1875,11 +1773,10 @@ int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfpla
     }
     if (int rc = e->ensure_streams(P.K, P.K)) return rc;
     P = plan_groups(e);
-    const int L = e->L();
-    const int steps = (e->cfg.num_simulations + L - 1) / L;
+    const int steps = e->steps();
     const EngineView E = e->view();
     const NetView N = net->view();
-    SelfplayParams sp{cfg->temperature_moves, cfg->temperature, cfg->opening_moves, cfg->emit_targets};
+    const SelfplayParams sp = selfplay_params(cfg);
     // Each group runs its own chain of searches and moves on its stream: its
     // move and the next search's first selection overlap the other groups'
     // last ResNet launches instead of waiting for a join after every move.
@@ -1894,7 +1791,7 @@ int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfpla
         for (int k = 0; k < P.K; ++k)
             launch_selfplay_move(E, sp, P.g0[k], P.ng[k], out(i, actions_dev, 1), out(i, finished_dev, 1),
                                  out(i, features_dev, 8 * C * 64), out(i, policy_dev, 8 * 65), P.st[k]);
-        if (timed) timing_end(e, steps + X, P.K, false, P);
+        if (timed) timing_end_search(e, steps + X, P);
     }
     if (rc) return rc;
     LAUNCHCHK();
@@ -1941,8 +1838,7 @@ static int arena_checks(const oamd_engine* a, const oamd_engine* b) {
 }
 
 static int arena_cfg_checks(const oamd_selfplay_config* cfg) {
-    if (!cfg || cfg->temperature_moves < 0 || !(cfg->temperature > 0.0f))
-        return fail(OAMD_INVALID_ARGUMENT, "arena: bad move config");
+    if (!cfg || !move_cfg_ok(cfg)) return fail(OAMD_INVALID_ARGUMENT, "arena: bad move config");
     return OAMD_OK;
 }
 
@@ -1983,10 +1879,10 @@ int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* n
     if (!actions_dev || !finished_dev || !discs_dev)
         return fail(OAMD_INVALID_ARGUMENT, "arena: actions, finished and discs buffers are required");
     DeviceGuard dg(a->device);
-    if (int rc = a->ensure_free_slots()) return rc;
+    if (int rc = a->ensure_remaining()) return rc;
     const int G = a->G;
     hipStream_t s = a->stream;
-    int32_t* remaining = a->remaining_dev;
+    int32_t* remaining = a->remaining.dev;
     // every byte 0xFF: action -1 in the plies that are never enqueued
     if (max_plies > 0) HIPCHK(hipMemsetAsync(actions_dev, 0xFF, sizeof(int32_t) * (size_t)max_plies * G, s));
     HIPCHK(hipMemsetAsync(finished_dev, 0, sizeof(int32_t) * G, s));
@@ -1997,9 +1893,9 @@ int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* n
     constexpr int kReadEvery = 8;  // plies between two reads of the matches still running
     int ply = 0;
     for (;;) {
-        HIPCHK(hipMemcpyAsync(a->remaining_host, remaining, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(a->remaining.host, remaining, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (a->remaining_host[0] <= 0 || ply >= max_plies) break;
+        if (a->remaining.host[0] <= 0 || ply >= max_plies) break;
         for (int k = 0; k < kReadEvery && ply < max_plies; ++k, ++ply) {
             // only the side to move of each match is active in its engine
             if (int rc = oamd_engine_search(a, net_a, nullptr, nullptr)) return rc;

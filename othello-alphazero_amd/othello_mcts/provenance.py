@@ -20,7 +20,7 @@ FAMILIES = {
     "resnet": ["resnet.hip", "kernels.h"],
     "tree": ["tree.hip", "engine.h", "bitboard.h", "rng.h", "kernels.h"],
     "all": ["bitboard.h", "capi.hip", "engine.h", "kernels.h", "replay.h", "replay.hip", "resnet.hip", "rng.h",
-            "solver.h", "solver.hip", "timing.h", "tree.hip",
+            "schedule.h", "solver.h", "solver.hip", "timing.h", "tree.hip",
             "../../include/othello_mcts_amd.h", "../../include/othello_mcts_amd_experimental.h"],
 }
 

@@ -2,12 +2,13 @@
 # Build liboamd.so variants HERE (CPU container) for the GPU-box recipes
 # `variants` / `benchvar` of tools/gpu.sh:
 #   VARIANTS="name:extra flags[:SRC];name2:..." bash tools/variants.sh
-# SRC: empty = the tree's resnet.hip with the tree's tree/capi objects; + =
+# SRC: empty = the tree's resnet.hip with the tree's other objects; + =
 # every unit of the working tree built with the flags;
-# a path = that resnet.hip with the tree's tree/capi objects; tree=PATH = that
+# a path = that resnet.hip with the tree's other objects; tree=PATH = that
 # tree.hip with the working tree's other units; @REV = all of
 # csrc/ and include/ at git revision REV (capi.hip packs the weights, so a
-# variant that changes the packing must bring its own capi). Built into
+# variant that changes the packing must bring its own capi). The units and
+# their flags are build.py's UNITS (resnet.hip's from RF). Built into
 # abv/<name>/liboamd.so (the pybind layer binds the C ABI, not the variant).
 set -eu
 cd "$(dirname "$0")/.."
@@ -15,8 +16,13 @@ B=othello-alphazero_amd/build
 CS=othello-alphazero_amd/csrc
 RF=${RF-"-mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-sched-strategy=max-ilp"}  # env RF overrides (scheduler A/Bs)
 CXX="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fno-gpu-rdc"
-EXACT="-ffp-contract=off -fno-fast-math"
-NOSCALAR="-mllvm -amdgpu-scalarize-global-loads=false"  # as build.py builds tree.hip
+# "unit flags..." per line, as build.py builds them (without the resource remarks its checks read)
+mapfile -t UNITS < <(OAMD_RESNET_FLAGS="$RF" python3 -c "
+import sys
+sys.path.insert(0, 'othello-alphazero_amd')
+import build
+for u, f in build.UNITS.items():
+    print(u, *[x for x in f if not x.startswith('-Rpass')])")
 rm -rf abv
 IFS=';' read -ra SETS <<< "${VARIANTS:?}"
 pids=()
@@ -25,29 +31,29 @@ for e in "${SETS[@]}"; do
   mkdir -p abv/$name
   (
     set -e
-    if [[ "${src:-}" == "+" ]]; then  # every unit of the working tree, built with the flags
-      $CXX -I $CS -I include $flags $RF -c $CS/resnet.hip -o abv/$name/resnet.o
-      $CXX -I $CS -I include $flags $EXACT $NOSCALAR -c $CS/tree.hip -o abv/$name/tree.o
-      $CXX -I $CS -I include $flags $EXACT -c $CS/capi.hip -o abv/$name/capi.o
-      objs="abv/$name/tree.o abv/$name/capi.o"
-    elif [[ "${src:-}" == tree=* ]]; then  # another tree.hip, the working tree's other units
-      $CXX -I $CS -I include $flags $RF -c $CS/resnet.hip -o abv/$name/resnet.o
-      $CXX -I $CS -I include $flags $EXACT $NOSCALAR -c ${src#tree=} -o abv/$name/tree.o
-      $CXX -I $CS -I include $flags $EXACT -c $CS/capi.hip -o abv/$name/capi.o
-      objs="abv/$name/tree.o abv/$name/capi.o"
-    elif [[ "${src:-}" == @* ]]; then
-      rev=${src#@}; d=abv/$name/src; mkdir -p $d
-      git archive "$rev" othello-alphazero_amd/csrc include | tar -x -C $d
-      inc="-I $d/$CS -I $d/include"
-      $CXX $inc $flags $RF -c $d/$CS/resnet.hip -o abv/$name/resnet.o
-      $CXX $inc $EXACT $NOSCALAR -c $d/$CS/tree.hip -o abv/$name/tree.o
-      $CXX $inc $EXACT -c $d/$CS/capi.hip -o abv/$name/capi.o
-      objs="abv/$name/tree.o abv/$name/capi.o"
-    else
-      $CXX -I $CS -I include $flags $RF -c ${src:-$CS/resnet.hip} -o abv/$name/resnet.o
-      objs="$B/tree.hip.o $B/capi.hip.o"
-    fi
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abv/$name/liboamd.so abv/$name/resnet.o $objs
+    dir=$CS inc="-I $CS -I include" every=1 rflags=$flags resnet= tree=
+    case "${src:-}" in
+      +) ;;                           # every unit of the working tree, built with the flags
+      tree=*) tree=${src#tree=} ;;    # another tree.hip, the working tree's other units
+      @*)                             # every unit at a revision (the flags: its resnet.hip only)
+        dir=abv/$name/src/$CS inc="-I $dir -I abv/$name/src/include" flags=
+        mkdir -p abv/$name/src
+        git archive "${src#@}" $CS include | tar -x -C abv/$name/src ;;
+      *) every=0 resnet=${src:-} ;;   # only resnet.hip (or the one given), the build's other objects
+    esac
+    objs=
+    for u in "${UNITS[@]}"; do
+      read -r unit uflags <<< "$u"
+      s=$dir/$unit f=$flags
+      if [[ $unit == resnet.hip ]]; then s=${resnet:-$s} f=$rflags
+      elif [[ $every == 0 ]]; then objs+=" $B/$unit.o"; continue
+      elif [[ $unit == tree.hip ]]; then s=${tree:-$s}
+      fi
+      [[ -f $s ]] || continue  # a revision from before the unit existed
+      $CXX $inc $f $uflags -c $s -o abv/$name/$unit.o
+      objs+=" abv/$name/$unit.o"
+    done
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abv/$name/liboamd.so $objs
     rm -rf abv/$name/*.o abv/$name/src
     echo "built $name"
   ) &
