@@ -63,11 +63,25 @@ int oamd_engine_set_adaptive_extra_rounds(oamd_engine *e, int32_t enable, int32_
  * over them instead of dispatching ~1000 mostly empty workgroups between the
  * other NN chain's. Scheduling only: results are identical. */
 int oamd_engine_set_extra_round_grid(oamd_engine *e, int32_t workgroups);
+/* Process-wide: which geometry of the fused ResNet kernel evaluates C=128
+ * launches of 1024 rows or more. enable != 0: 4 waves per workgroup, one per
+ * SIMD, each owning 32 channels x the 256 positions of the workgroup's 4
+ * boards, weight fragments queued in registers straight from L2
+ * (k_resnet_w4); 0: 8 waves of 32 channels x 128 positions fed from the LDS
+ * weight ring (k_resnet_w8). Takes effect at the next launch, for every net
+ * and engine of the process. Results do not depend on it, bit for bit.
+ * oamd_resnet_c128_four_wave returns the current setting (1 / 0). */
+int oamd_set_resnet_c128_four_wave(int32_t enable);
+int oamd_resnet_c128_four_wave(void);
 /* Diagnostics: copy the ResNet kernel's per-workgroup time stamps and cycle
  * sums (24 u64 per workgroup, resnet.hip kStampStride; see tools/nn_stamps.py)
  * of the last launch. Only in builds with OAMD_EXTRA_FLAGS=-DOAMD_STAMPS;
  * otherwise OAMD_INVALID_ARGUMENT. */
 int oamd_debug_read_stamps(uint64_t *out, int64_t n);
+/* Diagnostics: the engine keeps 16 guard words behind its policy and its value
+ * buffer (the outputs of the native search's ResNet launches); *intact = 1
+ * while no launch has written any of them (waits for the device). */
+int oamd_debug_eval_guards(oamd_engine *e, int32_t *intact);
 /* Diagnostics: k_tree's phase cycle sums over every wave since the last reset
  * (tools/tree_stamps.py); reset != 0 zeroes them after the copy. Only in
  * builds with OAMD_EXTRA_FLAGS=-DOAMD_TREE_STAMPS; otherwise

@@ -58,6 +58,10 @@ UNITS = {
 # k_resnet_w8 (8 waves, 2 per SIMD) must allocate <= 208 VGPRs per wave so one
 # k_select wave (93 VGPRs) still fits beside it on each SIMD (resnet.hip)
 W8_VGPR_LIMIT = 208
+# k_resnet_w4 (4 waves, 1 per SIMD): VGPRs + AGPRs of the SIMD's 512 unified
+# registers; 4 x 0 + 416 + the 96 of a k_tree wave = 512. No scratch: a spill
+# inside the tower would put memory traffic between its MFMAs.
+W4_VGPR_LIMIT = 416
 
 
 def run(cmd: list[str]) -> None:
@@ -117,7 +121,31 @@ def check_w8_vgprs(remarks: str) -> None:
         sys.stderr.write("note: no k_resnet_w8 kernel in this build\n")
 
 
-RESOURCE_CHECKS = {"resnet.hip": check_w8_vgprs, "solver.hip": check_solver_scratch}
+def check_w4_resources(remarks: str) -> None:
+    """k_resnet_w4 (not its extra-round loop kernel, which runs nearly empty
+    launches): VGPRs + AGPRs (granule 8) <= W4_VGPR_LIMIT and no scratch."""
+    regs: dict[str, int] = {}
+    for name, field, value in kernel_remarks(remarks):
+        if "k_resnet_w4" not in name or "k_resnet_w4_loop" in name:
+            continue
+        if field in ("VGPRs", "AGPRs"):
+            regs[name] = regs.get(name, 0) + (int(value.split()[0]) + 7) // 8 * 8
+        elif field.startswith("ScratchSize") and int(value.split()[0]) != 0:
+            raise SystemExit(f"build failed: {name} uses {value} bytes of scratch per lane")
+    for name, v in regs.items():
+        if v > W4_VGPR_LIMIT:
+            raise SystemExit(f"build failed: {name} uses {v} VGPRs + AGPRs (> {W4_VGPR_LIMIT}): "
+                             "a k_tree wave could no longer co-reside with the ResNet kernel")
+    if not regs:
+        raise SystemExit("build failed: no resource remark for k_resnet_w4 in resnet.hip")
+
+
+def check_resnet(remarks: str) -> None:
+    check_w8_vgprs(remarks)
+    check_w4_resources(remarks)
+
+
+RESOURCE_CHECKS = {"resnet.hip": check_resnet, "solver.hip": check_solver_scratch}
 
 
 def newer(out: Path, deps: list[Path]) -> bool:

@@ -417,6 +417,8 @@ struct oamd_engine {
         return OAMD_OK;
     }
 
+    static constexpr int kEvalGuard = 16;  // guard floats behind policy / value
+    static constexpr int kEvalGuardByte = 0x5A;
     int L() const { return cfg.num_threads * cfg.batch_size; }
     int steps() const { return search_steps(cfg.num_simulations, L()); }
     // thread-split schedule for one game (OAMD_TREE_SPLIT=0 in the environment: off)
@@ -503,11 +505,15 @@ struct oamd_engine {
         int rc;
         if ((rc = dalloc(&leaf, rows)) || (rc = dalloc(&depth, rows)) || (rc = dalloc(&trans, rows)) ||
             (rc = dalloc(&path, rows * kMaxDepth)) || (rc = dalloc(&feat, rows * fw)) ||
-            (rc = dalloc(&policy, rows * 65)) || (rc = dalloc(&value, rows)) || (rc = dalloc(&flags, rows)) ||
+            (rc = dalloc(&policy, rows * 65 + kEvalGuard)) || (rc = dalloc(&value, rows + kEvalGuard)) ||
+            (rc = dalloc(&flags, rows)) ||
             (rc = dalloc(&rowlist, rows)) || (rc = dalloc(&tstate, rows)))
             return rc;
         HIPCHK(hipMemset(policy, 0, rows * 65 * sizeof(float)));
         HIPCHK(hipMemset(value, 0, rows * sizeof(float)));
+        // guard words behind both (oamd_debug_eval_guards): no launch writes them
+        HIPCHK(hipMemset(policy + rows * 65, kEvalGuardByte, kEvalGuard * sizeof(float)));
+        HIPCHK(hipMemset(value + rows, kEvalGuardByte, kEvalGuard * sizeof(float)));
         rows_cap = rows;
         fw_cap = fw;
         return OAMD_OK;
@@ -1443,6 +1449,28 @@ int oamd_engine_set_pipeline(oamd_engine* e, int32_t groups) {
     if (groups < 0 || groups > kMaxPipeline)
         return fail(OAMD_INVALID_ARGUMENT, "pipeline groups must be in [0, " + std::to_string(kMaxPipeline) + "]");
     e->pipeline = groups;
+    return OAMD_OK;
+}
+
+int oamd_set_resnet_c128_four_wave(int32_t enable) {
+    resnet_set_c128_four_wave(enable);
+    return OAMD_OK;
+}
+
+int oamd_resnet_c128_four_wave(void) { return resnet_c128_four_wave(); }
+
+int oamd_debug_eval_guards(oamd_engine* e, int32_t* intact) {
+    if (!e || !intact) return fail(OAMD_INVALID_ARGUMENT, "eval guards: null argument");
+    DeviceGuard dg(e->device);
+    *intact = 1;
+    if (!e->policy || !e->value) return OAMD_OK;
+    HIPCHK(hipDeviceSynchronize());
+    unsigned char g[2][oamd_engine::kEvalGuard * sizeof(float)];
+    HIPCHK(hipMemcpy(g[0], e->policy + e->rows_cap * 65, sizeof(g[0]), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(g[1], e->value + e->rows_cap, sizeof(g[1]), hipMemcpyDeviceToHost));
+    for (auto& b : g)
+        for (unsigned char c : b)
+            if (c != oamd_engine::kEvalGuardByte) *intact = 0;
     return OAMD_OK;
 }
 

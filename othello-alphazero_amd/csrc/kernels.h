@@ -104,6 +104,11 @@ size_t resnet_packed_weight_alloc_elems(int C, int R);  // + the zero pad the st
 size_t resnet_head_floats(int C, int hidden);
 // elements of the packed 1x1 head-conv fragments (NetView::hconv)
 inline size_t resnet_hconv_elems(int C) { return (size_t)(C / 32) * 64 * 8; }
+// C=128 throughput launches (>= 1024 rows) on the 4-wave register-queue
+// geometry (nonzero) or the 8-wave ring geometry (0); process-wide, results
+// are bit-identical (oamd_set_resnet_c128_four_wave)
+void resnet_set_c128_four_wave(int enable);
+int resnet_c128_four_wave();
 // diagnostic stamp buffer (OAMD_STAMPS builds; -2 otherwise), see resnet.hip
 int resnet_read_stamps(unsigned long long* out, long long n);
 int tree_read_stamps(unsigned long long* out, long long n, int reset);

@@ -451,6 +451,8 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
     m.def("get_flips", &oamd_host_flips, "move_mask"_a, "player_discs"_a, "opponent_discs"_a);
     m.def("device_count", &device_count);
     m.def("abi_version", &oamd_abi_version);
+    m.def("set_resnet_c128_four_wave", [](bool enable) { check(oamd_set_resnet_c128_four_wave(enable ? 1 : 0)); });
+    m.def("resnet_c128_four_wave", []() { return oamd_resnet_c128_four_wave() != 0; });
     m.def("source_hash", [](const std::string& family) {
         const char* h = oamd_source_hash(family.c_str());
         if (!h) throw py::value_error("unknown source family: " + family);
@@ -713,6 +715,11 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
             int64_t searches = 0, rounds = 0, finals = 0;
             check(oamd_engine_round_counts(e.h, &searches, &rounds, &finals));
             return py::make_tuple(searches, rounds, finals);
+        })
+        .def("eval_guards_intact", [](Engine& e) {
+            int32_t ok = 0;
+            check(oamd_debug_eval_guards(e.h, &ok));
+            return ok != 0;
         })
         .def("set_free_running",
              [](Engine& e, bool enable) { check(oamd_engine_set_free_running(e.h, enable ? 1 : 0)); })

@@ -4,7 +4,10 @@
 // Work decomposition (DESIGN.md "ResNet kernel"):
 //   * a 512-thread workgroup (8 waves, 2 per SIMD) owns BOARDS = 512/C boards
 //     (4 boards at C=128, 2 boards at C=256) and runs the whole tower + both
-//     heads on them; activations never leave LDS;
+//     heads on them; activations never leave LDS; the default C=128
+//     throughput geometry is a 256-thread workgroup instead (4 waves, one per
+//     SIMD, GeoW4 below): same 4 boards, each wave 32 channels x all 256
+//     positions, weights from L2 into a register queue instead of the ring;
 //   * each 3x3 conv is an implicit GEMM  out[ch][pos] = W[ch][K] x X[K][pos],
 //     K = 9 taps x C_in, on v_mfma_f32_16x16x32_{bf16,f16} with the WEIGHTS as
 //     the A operand: an accumulator lane then holds 4 consecutive output
@@ -33,6 +36,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -92,7 +96,8 @@ constexpr int kStageBytes = 16384;
 // 6.385 ms vs 6.725 with the ring; a 2-deep queue 6.51; 6- and 8-deep queues
 // spill. At C=128 (one barrier per 2 K-steps, and the two board pairs' waves
 // of a channel block fetch the same fragments) the queue measured 1.3 %
-// slower than the ring: 0.807-0.809 vs 0.794-0.798 ms.
+// slower than the ring: 0.807-0.809 vs 0.794-0.798 ms. The 4-wave C=128
+// geometry (GeoW4) fetches each fragment once per workgroup and uses the queue.
 constexpr int kWeightQueue = 4;
 constexpr int kStageBytesMax = 32768;
 __host__ __device__ constexpr int stage_bytes(int C) { return C == 256 ? OAMD_C256_STAGE : OAMD_C128_STAGE; }
@@ -226,6 +231,14 @@ constexpr TilePos make_tile_pos() {
 }
 __constant__ TilePos kTilePos = make_tile_pos();
 
+// heads(): fp32 scratch of a workgroup of B boards (the drained weight ring,
+// or the LDS behind the activations of a geometry without one)
+constexpr int kMaxValueHidden = 1024;  // scratch budget (capi.hip validates)
+template <int B>
+__host__ __device__ constexpr int head_scratch_floats(int hidden) {
+    return 128 * B + 64 * B + 4 * B * 64 + 2 * B * ((hidden + 63) / 64) * 64;
+}
+
 // Edge-row tiling (G::EDGE): layout row of B-fragment column j of position tile
 // m for position group q (wave / WN). Group q = (pair P, half h): tile m is
 // board row y = 4h + m of boards P and P + NPAIR (NPAIR * BROWS = 8 mod 16 rows
@@ -237,11 +250,15 @@ __constant__ TilePos kTilePos = make_tile_pos();
 // boards keep no top / bottom border rows (G::ROW0 = 0): the MFMAs of tile 0
 // at dy = -1 and tile 7 at dy = +1 are left out, so rows -1 and 8 are never
 // read; the left / right border columns stay (zero) in every row.
+// A wave of G::MT / 8 > 1 pairs (the 4-wave geometry) takes its tiles 8i ..
+// 8i + 7 from group q * (MT / 8) + i.
 template <class G>
 __host__ __device__ constexpr int edge_tile_row(int q, int m, int j) {
     constexpr int NP = G::NPAIR > 0 ? G::NPAIR : 1;
-    const int P = q % NP, h = q / NP;
-    const int y = 4 * h + m;
+    constexpr int PPW = G::MT >= 8 ? G::MT / 8 : 1;  // pairs per wave
+    const int g = q * PPW + m / 8;
+    const int P = g % NP, h = g / NP;
+    const int y = 4 * h + m % 8;
     const int r0 = (P * G::BROWS + G::ROW0 + y * 10 + 1) & 15;
     const int oddcol = (j < 4 || j >= 12) ? 1 : 0;
     const int b = j < 8 ? P : P + NP;
@@ -270,7 +287,9 @@ struct GeoT {
     // 104, so the two boards of an edge tile sit 8 rows apart modulo 16
     static constexpr int NPAIR = BOARDS / 2;
     // edge-row wave tiles (32 channels x rows 0-7 of a board pair)
-    static constexpr bool EDGE = BOARDS >= 2 && BOARDS % 2 == 0 && WC_ == 32 && PW_ == 128;
+    // (PW = 256: both board pairs of a 4-board workgroup on one wave)
+    static constexpr bool EDGE = BOARDS >= 2 && BOARDS % 2 == 0 && WC_ == 32 && (PW_ == 128 || PW_ == 256);
+    static constexpr int PAIRS = EDGE ? PW_ / 128 : 1;  // board pairs per wave
     // layout row of board row y, column x (x = -1, 8: the zero border) is
     // b * BROWS + ROW0 + 10 y + x + 1. Edge-row boards: 8 rows of 10 (no top /
     // bottom border), BROWS = 84 / 88 so the boards of a tile pair sit 8 rows
@@ -281,7 +300,11 @@ struct GeoT {
     static constexpr int ACT_BYTES = BOARDS * BROWS * RP;
     // DIRECT: no weight ring during the tower (its LDS stays allocated as the
     // heads' scratch); WQ = K-steps of weight fragments held per wave
-    static constexpr bool DIRECT = EDGE && C == 256;
+    static constexpr bool DIRECT = EDGE && (C == 256 || PAIRS == 2);
+    // NORING: no ring at all, the LDS behind the activations is only the
+    // heads' scratch (the 4-wave geometry)
+    static constexpr bool NORING = PAIRS == 2;
+    static constexpr int SCRATCH = head_scratch_floats<BOARDS_>(kMaxValueHidden) * 4;
     static constexpr int WQ = kWeightQueue;
     static constexpr int KSTEP_BYTES = 32 * C * 2;
     static constexpr int STAGE = STAGE_;
@@ -289,7 +312,7 @@ struct GeoT {
     static constexpr int DPT = STAGE / 16 / THREADS;         // DMAs per thread per stage
     static constexpr int RING_FIT = (kLdsBytes - ACT_BYTES) / STAGE;
     static constexpr int RING = RING_FIT < RING_MAX_ ? RING_FIT : RING_MAX_;  // weight ring slots
-    static constexpr int LDS = ACT_BYTES + RING * STAGE;
+    static constexpr int LDS = ACT_BYTES + (NORING ? SCRATCH : RING * STAGE);
     // The barrier that opens stage s issues stage s + AHEAD. Every wave has
     // retired its reads of stage s-1 before that barrier (the per-step
     // lgkmcnt(0) fence), so s-1's slot is free and AHEAD = RING - 1 stages fly
@@ -313,13 +336,21 @@ struct GeoT {
     static_assert(KS == 1 || KS == 2 || KS == 4, "K-steps per stage");
     static_assert(ksteps_first(C) % KS == 0 && ksteps_tower(C) % KS == 0, "whole stages per layer");
     static_assert(THREADS >= BOARDS * 64 && DPT >= 1 && VM_LAYER <= 63, "decomposition");
-    static_assert(!EDGE || ((NPAIR * BROWS) % 16 == 8 && WAVES == 8), "edge tiles: pair boards 8 rows apart mod 16");
+    static_assert(!EDGE || ((NPAIR * BROWS) % 16 == 8 && WAVES * PAIRS == 8), "edge tiles: pair boards 8 rows apart mod 16");
+    static_assert(!NORING || (DIRECT && NPAIR == 2 && BROWS % 2 == 0 && ACT_BYTES % 16 == 0), "two pairs per wave");
     static_assert(!DIRECT || ((3 * (C / 32)) % WQ == 0 && WQ >= 2), "register queue: whole queues per dx");
 };
 // throughput geometry: 512 positions x C channels per workgroup, 8 waves of
 // 32 channels x 128 positions (edge-row tiles)
 template <int C>
 using Geo = GeoT<C, 512 / C, 32, C == 128 ? OAMD_C128_RING : OAMD_C256_RING, stage_bytes(C), 128>;
+// C=128 throughput geometry on 4 waves, one per SIMD: a wave owns 32 channels x
+// the 256 positions of the workgroup's 4 boards (tiles 0-7: board pair 0, tiles
+// 8-15: board pair 1) and takes its weight fragments from L2 into a register
+// queue (DIRECT), so each fragment is fetched once per workgroup and feeds 16
+// MFMAs; no weight ring, no LDS-DMA, no stage barriers. STAGE
+// only fixes the first conv's K-step count (the packed weights' pad step).
+using GeoW4 = GeoT<128, 4, 32, OAMD_C128_RING, stage_bytes(128), 256>;
 // small-batch geometry (latency): one board per workgroup, 8 waves of C/8
 // channels, so a handful of rows spreads over as many CUs as boards. 8 waves
 // take 0.098 ms per 16-32 rows against 0.107 with 4 (two same-box pairs,
@@ -501,11 +532,6 @@ __device__ __forceinline__ void lds_barrier() {
 //            reduction over squares), softmax(65) / ReLU, Linear(hidden->1), tanh.
 // Every output's arithmetic order is independent of BOARDS / WAVES, so all
 // geometries produce identical bits.
-constexpr int kMaxValueHidden = 1024;  // scratch budget (capi.hip validates)
-template <int B>
-__host__ __device__ constexpr int head_scratch_floats(int hidden) {
-    return 128 * B + 64 * B + 4 * B * 64 + 2 * B * ((hidden + 63) / 64) * 64;
-}
 
 #ifdef OAMD_STAMPS
 // Diagnostic build only (tools/nn_stamps.py): per workgroup, wave 0 lane 0
@@ -554,7 +580,7 @@ __device__ __forceinline__ void heads(const NetView& N, const unsigned char* act
     constexpr int C = G::C;
     constexpr int B = G::BOARDS;
     constexpr int NW = G::WAVES;
-    static_assert(head_scratch_floats<B>(kMaxValueHidden) * 4 <= G::RING * G::STAGE, "head scratch");
+    static_assert(head_scratch_floats<B>(kMaxValueHidden) * 4 <= G::LDS - G::ACT_BYTES, "head scratch");
     // opaque to the optimiser: keeps the heads' lane-derived addresses from
     // being hoisted to the kernel start and held live through the tower
     asm volatile("" : "+v"(lane));
@@ -795,11 +821,20 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
     // epilogue writes (row + k-group's 8-byte half chunk), weight fragments
     // (edge-row tiles: tile m is board row m, one lane base + m x 10 rows, so
     // every tile's offset folds into the LDS instructions' immediates)
+    // kPT tiles per board pair, kNP pairs per wave: pair p's tiles are pair
+    // 0's, one board (kPairB bytes) further on (edge_tile_row: boards P and
+    // P + NPAIR, same columns since BROWS is even)
+    constexpr int kPT = G::EDGE ? 8 : kMT;
+    constexpr int kNP = kMT / kPT;
+    constexpr int kPairB = G::BROWS * G::RP;
+    static_assert(kNP == 1 || (edge_tile_row<G>(0, 8, 0) == edge_tile_row<G>(0, 0, 0) + G::BROWS &&
+                               edge_tile_row<G>(0, 15, 13) == edge_tile_row<G>(0, 7, 13) + G::BROWS),
+                  "pair bases one board apart");
     int rd[kMT], wr[kMT];
     const int erow0 = G::EDGE ? edge_tile_row<G>(wm, 0, lane & 15) * G::RP : 0;
 #pragma unroll
     for (int m = 0; m < kMT; ++m) {
-        const int rowb = G::EDGE ? erow0 + m * 10 * G::RP
+        const int rowb = G::EDGE ? erow0 + (m / kPT) * kPairB + (m % kPT) * 10 * G::RP
                                  : (wm * G::BROWS + G::prow(kTilePos.p[16 * m + (lane & 15)])) * G::RP;
         rd[m] = rowb + kgroup_chunk(kg) * 16;
         wr[m] = rowb;
@@ -900,7 +935,8 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
     // edge-row tiles: the activation fragments of the current / next channel
     // block come from register windows of board rows (fa / fb carry weights)
     constexpr bool kWide = G::EDGE;
-    u32x4_t win0[kWide ? 9 : 1], win1[kWide ? 9 : 1];
+    // (one window pair per board pair of the wave)
+    u32x4_t win0[kNP][kWide ? 9 : 1], win1[kNP][kWide ? 9 : 1];
     // window base: this lane's column, board row -1, dx = -1
     const int sb0 = rd[0] - 10 * G::RP - G::RP;
     int slot = 0;  // ring slot of the stage holding the current K-step
@@ -931,8 +967,10 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
     // the first conv's K-step 0 (tap 0, dy = -1: edge-row geometries skip tile 0)
     if constexpr (!G::DIRECT) load_wfrags(fa, ring, wl);
 #pragma unroll
-    for (int m = kWide ? 1 : 0; m < kMT; ++m)
-        fa.x[m] = *reinterpret_cast<const u32x4_t*>(act + first_kstep_offset<C>(0) + rd[m]);
+    for (int p = 0; p < kNP; ++p)
+#pragma unroll
+        for (int m = kWide ? 1 : 0; m < kPT; ++m)
+            fa.x[p * kPT + m] = *reinterpret_cast<const u32x4_t*>(act + first_kstep_offset<C>(0) + rd[p * kPT + m]);
     OAMD_STAMP(1);
 #ifdef OAMD_STAMPS
     const unsigned long long tower_t0 = __builtin_amdgcn_s_memtime();
@@ -973,8 +1011,8 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
         // i1-1). KIS: i1's K-step within its stage (0: i1 opens a new stage ->
         // DMA wait + barrier, ring advances). TILES = xlo | xhi << 4 | mlo << 8 |
         // mhi << 12: position tiles [xlo, xhi) of nxt are read and MFMAs run on
-        // tiles [mlo, mhi) of cur (edge-row geometries leave out the border
-        // tiles of the first conv). xoff: uniform byte offset of the next
+        // tiles [mlo, mhi) of cur, of each board pair of the wave (edge-row
+        // geometries leave out the border tiles of the first conv). xoff: uniform byte offset of the next
         // K-step's activation rows/channels
         auto step = [&](auto KIS, auto TILES, auto GI, const Frags<kNT, kMT>& cur, Frags<kNT, kMT>& nxt, int xoff) {
             constexpr int kis = decltype(KIS)::value;
@@ -996,7 +1034,10 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
             {
                 const unsigned char* ap = act + xoff;
 #pragma unroll
-                for (int m = xlo; m < xhi; ++m) nxt.x[m] = *reinterpret_cast<const u32x4_t*>(ap + rd[m]);
+                for (int p = 0; p < kNP; ++p)
+#pragma unroll
+                    for (int m = xlo; m < xhi; ++m)
+                        nxt.x[p * kPT + m] = *reinterpret_cast<const u32x4_t*>(ap + rd[p * kPT + m]);
             }
             if constexpr (open) {
                 // open the next stage: it has landed (this wave's DMAs, then
@@ -1019,16 +1060,18 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
 #pragma unroll
             for (int n = 0; n < kNT; ++n)
 #pragma unroll
-                for (int m = mlo; m < mhi; ++m) {
-                    if constexpr (G::DIRECT) acc[n][m] = mfma<DT>(wq[gi % WQ][n], cur.x[m], acc[n][m]);
-                    else acc[n][m] = mfma<DT>(cur.w[n], cur.x[m], acc[n][m]);
-                }
+                for (int p = 0; p < kNP; ++p)
+#pragma unroll
+                    for (int m = p * kPT + mlo; m < p * kPT + mhi; ++m) {
+                        if constexpr (G::DIRECT) acc[n][m] = mfma<DT>(wq[gi % WQ][n], cur.x[m], acc[n][m]);
+                        else acc[n][m] = mfma<DT>(cur.w[n], cur.x[m], acc[n][m]);
+                    }
             // fine interleave of the step's fragment reads with its MFMAs (one
             // read, then a share of the MFMAs; +2.5 %): a stage-opening step has
             // only its weight reads after the barrier
             if constexpr (G::DIRECT) {
-                constexpr int nds = xhi - xlo;
-                constexpr int nm = kNT * (mhi - mlo);
+                constexpr int nds = kNP * (xhi - xlo);
+                constexpr int nm = kNP * kNT * (mhi - mlo);
                 static_for<nds>([&](auto I) {
                     constexpr int i = decltype(I)::value;
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -1051,14 +1094,14 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
             }
         };
         // all tiles read and multiplied
-        using AllTiles = std::integral_constant<int, kMT << 4 | kMT << 12>;
+        using AllTiles = std::integral_constant<int, kPT << 4 | kPT << 12>;
         if constexpr (first) {
             // tap-major, K-step i = tap min(i, 8) (the pad steps repeat tap 8
             // with zero weights); edge-row geometries leave out tile 0 at
             // dy = -1 and tile 7 at dy = +1 (rows -1 and 8 are not in the layout)
             auto tiles = [](int i) {
                 const int dy = (i < 9 ? i : 8) / 3 - 1;
-                const int lo = kWide && dy < 0 ? 1 : 0, hi = kWide && dy > 0 ? kMT - 1 : kMT;
+                const int lo = kWide && dy < 0 ? 1 : 0, hi = kWide && dy > 0 ? kPT - 1 : kPT;
                 return lo | hi << 4 | lo << 8 | hi << 12;
             };
             static_for<nk - 1>([&](auto II) {
@@ -1076,13 +1119,15 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
 #pragma unroll
             for (int n = 0; n < kNT; ++n)
 #pragma unroll
-                for (int m = ml; m < mh; ++m) {
-                    if constexpr (G::DIRECT) acc[n][m] = mfma<DT>(wq[(nk - 1) % WQ][n], last.x[m], acc[n][m]);
-                    else acc[n][m] = mfma<DT>(last.w[n], last.x[m], acc[n][m]);
-                }
+                for (int p = 0; p < kNP; ++p)
+#pragma unroll
+                    for (int m = p * kPT + ml; m < p * kPT + mh; ++m) {
+                        if constexpr (G::DIRECT) acc[n][m] = mfma<DT>(wq[(nk - 1) % WQ][n], last.x[m], acc[n][m]);
+                        else acc[n][m] = mfma<DT>(last.w[n], last.x[m], acc[n][m]);
+                    }
         } else if constexpr (kWide) {
             constexpr int KPT = C / 32;
-            static_assert(kNT == 2 && kMT == 8 && KPT % 2 == 0 && (3 * KPT) % G::KS == 0, "wide geometry");
+            static_assert(kNT == 2 && kPT == 8 && KPT % 2 == 0 && (3 * KPT) % G::KS == 0, "wide geometry");
             constexpr int NJ = 3 * KPT;     // K-steps per dx
             constexpr int RS = 10 * G::RP;  // one board row
             // K-step J = (cb J/3, dy J%3 - 1) of the dx: tiles mlo..mhi-1 from
@@ -1100,18 +1145,18 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
                     decltype(LASTDX)::value ? wide_new_last<OAMD_EPI_NOBAR && !G::DIRECT>(Jn, NJ) : wide_new(Jn);
                 constexpr int dy = wide_dy(J), cbn = wide_cb(Jn), nnew = __builtin_popcount(newmask);
                 constexpr int mlo = dy < 0 ? 1 : 0, mhi = dy > 0 ? 7 : 8;
-                auto& Wc = [&]() -> u32x4_t(&)[9] {
+                auto& Wc = [&]() -> u32x4_t(&)[kNP][9] {
                     if constexpr (wide_cb(J) % 2 == 0) return win0; else return win1;
                 }();
-                auto& Wn = [&]() -> u32x4_t(&)[9] {
+                auto& Wn = [&]() -> u32x4_t(&)[kNP][9] {
                     if constexpr (cbn % 2 == 0) return win0; else return win1;
                 }();
                 __builtin_amdgcn_sched_barrier(0);
                 OAMD_STEP_WAIT(__builtin_amdgcn_s_waitcnt(0xC07F));  // lgkmcnt(0): wc / Wc have landed
-                static_for<9>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
+                static_for<9 * kNP>([&](auto I) {
+                    constexpr int p = decltype(I)::value / 9, i = decltype(I)::value % 9;
                     if constexpr ((newmask >> i) & 1)
-                        Wn[i] = *reinterpret_cast<const u32x4_t*>(act + sbn + i * RS + cbn * 64);
+                        Wn[p][i] = *reinterpret_cast<const u32x4_t*>(act + sbn + p * kPairB + i * RS + cbn * 64);
                 });
                 if constexpr (open) {
                     OAMD_OPEN_WAIT(wait_vm<G::VM_OPEN>(), __builtin_amdgcn_s_barrier());
@@ -1126,15 +1171,19 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
                 }
                 if constexpr (G::DIRECT) wload(std::integral_constant<int, WOFF + J + WQ - 1>{});
                 else load_wfrags(wn, ring + slot * G::STAGE + (Jn % G::KS) * G::KSTEP_BYTES, wl);
+                // both pairs' MFMAs of the K-step from the one set of weight fragments
 #pragma unroll
                 for (int n = 0; n < kNT; ++n)
 #pragma unroll
-                    for (int m = mlo; m < mhi; ++m) {
-                        if constexpr (G::DIRECT) acc[n][m] = mfma<DT>(wq[(WOFF + J) % WQ][n], Wc[m + 1 + dy], acc[n][m]);
-                        else acc[n][m] = mfma<DT>(wc.w[n], Wc[m + 1 + dy], acc[n][m]);
-                    }
-                constexpr int nds = G::DIRECT ? nnew : (open ? kNT : kNT + nnew);
-                constexpr int nm = kNT * (mhi - mlo);
+                    for (int p = 0; p < kNP; ++p)
+#pragma unroll
+                        for (int m = mlo; m < mhi; ++m) {
+                            f32x4_t& a = acc[n][p * kPT + m];
+                            if constexpr (G::DIRECT) a = mfma<DT>(wq[(WOFF + J) % WQ][n], Wc[p][m + 1 + dy], a);
+                            else a = mfma<DT>(wc.w[n], Wc[p][m + 1 + dy], a);
+                        }
+                constexpr int nds = G::DIRECT ? kNP * nnew : (open ? kNT : kNT + nnew);
+                constexpr int nm = kNP * kNT * (mhi - mlo);
                 static_for<nds>([&](auto I) {
                     constexpr int i = decltype(I)::value;
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -1156,10 +1205,13 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
 #pragma unroll
                     for (int n = 0; n < kNT; ++n)
 #pragma unroll
-                        for (int m = 0; m < 7; ++m) {
-                            if constexpr (G::DIRECT) acc[n][m] = mfma<DT>(wq[(WOFF + NJ - 1) % WQ][n], win1[m + 2], acc[n][m]);
-                            else acc[n][m] = mfma<DT>(fb.w[n], win1[m + 2], acc[n][m]);
-                        }
+                        for (int p = 0; p < kNP; ++p)
+#pragma unroll
+                            for (int m = 0; m < 7; ++m) {
+                                f32x4_t& a = acc[n][p * kPT + m];
+                                if constexpr (G::DIRECT) a = mfma<DT>(wq[(WOFF + NJ - 1) % WQ][n], win1[p][m + 2], a);
+                                else a = mfma<DT>(fb.w[n], win1[p][m + 2], a);
+                            }
                 }
             };
 #pragma nounroll
@@ -1203,6 +1255,9 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
         // opened its last stage (wide_new_last), so the stores need no barrier;
         // the last stage's slot is refilled after the post-store barrier
         constexpr bool nobar = OAMD_EPI_NOBAR && kWide && !first && !G::DIRECT;
+        // with more K-steps per stage, window reads of the last (dx, block)
+        // would follow the barrier that opens the layer's last stage
+        static_assert(!nobar || G::KS <= 2, "OAMD_EPI_NOBAR: at most 2 K-steps per stage");
         const int last_slot = slot;  // the slot of the layer's last stage
         if constexpr (!nobar) {
             lds_barrier();  // every wave is done reading this layer's input and its last stage
@@ -1254,7 +1309,10 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
             if constexpr (kWide) {
                 if constexpr (!G::DIRECT) load_wfrags(fa, ring + slot * G::STAGE, wl);
 #pragma unroll
-                for (int i = 1; i < 8; ++i) win0[i] = *reinterpret_cast<const u32x4_t*>(act + sb0 + i * 10 * G::RP);
+                for (int p = 0; p < kNP; ++p)
+#pragma unroll
+                    for (int i = 1; i < 8; ++i)
+                        win0[p][i] = *reinterpret_cast<const u32x4_t*>(act + sb0 + p * kPairB + i * 10 * G::RP);
             } else {
                 load_frags(fa, act, ring + slot * G::STAGE, tower_kstep0_offset<C>(), rd, wl);
             }
@@ -1288,7 +1346,7 @@ __device__ __forceinline__ void resnet_body(NetView N, const void* __restrict__ 
     OAMD_STAMP(3);
 }
 
-// Every geometry is 8 waves (2 per SIMD), capped at 208 VGPRs: that leaves 96
+// The 8-wave geometries (2 waves per SIMD) are capped at 208 VGPRs: that leaves 96
 // of a SIMD's 512 for one k_tree wave (<= 96 VGPRs, no LDS), so the other
 // pipeline group's tree kernel co-resides with this kernel instead of waiting
 // for a CU. amdgpu_num_vgpr counts in units of the unified VGPR+AGPR file on
@@ -1336,13 +1394,59 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(OAMD_VGPR_CAP))
     }
 }
 
+// The 4-wave geometry (GeoW4): one wave per SIMD, capped at 416 VGPRs of the
+// SIMD's 512 (amdgpu_num_vgpr counts half of the unified file, see above), so
+// the 96-VGPR k_tree wave still fits beside it; build.py checks the
+// allocation and that nothing spills to scratch.
+#ifndef OAMD_W4_VGPR_CAP
+#define OAMD_W4_VGPR_CAP 208
+#endif
+template <class G, int DT, int IN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(OAMD_W4_VGPR_CAP))) void k_resnet_w4(
+    NetView N, const void* __restrict__ feat_in, int fw, int H, RowMap M, float* __restrict__ policy,
+    float* __restrict__ value) {
+    if (M.span && threadIdx.x == 0) atomicMax(M.span, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
+    resnet_body<G, DT, IN>(N, feat_in, fw, H, M, policy, value, blockIdx.x);
+    if (M.span) {
+        __syncthreads();
+        if (threadIdx.x == 0) atomicMax(M.span + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
+}
+
+template <class G, int DT, int IN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(OAMD_W4_VGPR_CAP))) void k_resnet_w4_loop(
+    NetView N, const void* __restrict__ feat_in, int fw, int H, RowMap M, float* __restrict__ policy,
+    float* __restrict__ value) {
+    if (M.span && threadIdx.x == 0) atomicMax(M.span, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
+    int rows = M.rows;
+    if (M.list) {
+        const int filled = *M.count - M.off;
+        rows = filled < rows ? (filled > 0 ? filled : 0) : rows;
+    }
+    for (int wg = blockIdx.x; wg * G::BOARDS < rows; wg += gridDim.x) {
+        resnet_body<G, DT, IN>(N, feat_in, fw, H, M, policy, value, wg);
+        __syncthreads();  // the heads' scratch is read before the next group's activations land
+    }
+    if (M.span) {
+        __syncthreads();
+        if (threadIdx.x == 0) atomicMax(M.span + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
+}
+
+// the geometry's kernel (LOOP: its extra-round loop kernel): only that one is instantiated
+template <class G, int DT, int IN, bool LOOP>
+static constexpr auto kernel_of() {
+    if constexpr (G::THREADS == 256) return LOOP ? &k_resnet_w4_loop<G, DT, IN> : &k_resnet_w4<G, DT, IN>;
+    else return LOOP ? &k_resnet_w8_loop<G, DT, IN> : &k_resnet_w8<G, DT, IN>;
+}
+
 template <class G, int DT, int IN>
 static void launch_t(const NetView& N, const void* feat, int fw, int H, const RowMap& M, float* pol, float* val,
                      hipStream_t s, int max_wgs) {
     const int rows = M.rows;
-    static_assert(G::THREADS == 512, "k_resnet_w8 geometries");
+    static_assert(G::THREADS == 512 || (G::THREADS == 256 && G::NORING), "k_resnet_w8 / k_resnet_w4 geometries");
     const unsigned grid = (unsigned)((rows + G::BOARDS - 1) / G::BOARDS);
-    constexpr auto kern = &k_resnet_w8<G, DT, IN>;
+    constexpr auto kern = kernel_of<G, DT, IN, false>();
     static bool configured = false;
     if (!configured) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1351,7 +1455,7 @@ static void launch_t(const NetView& N, const void* feat, int fw, int H, const Ro
     }
     if constexpr (IN == kPacked) {
         if (max_wgs > 0 && grid > (unsigned)max_wgs) {
-            constexpr auto lk = &k_resnet_w8_loop<G, DT, IN>;
+            constexpr auto lk = kernel_of<G, DT, IN, true>();
             static bool lconfigured = false;
             if (!lconfigured) {
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lk),
@@ -1371,6 +1475,16 @@ static void launch_t(const NetView& N, const void* feat, int fw, int H, const Ro
 // tiling per output are the same, so results are bit-identical.
 constexpr int kSmallBatchRows = 1024;
 
+// C=128 throughput launches: the 4-wave register-queue geometry (GeoW4) or the
+// 8-wave ring geometry (Geo<128>); process-wide, for A/B measurements
+// (oamd_set_resnet_c128_four_wave). Bit-identical either way.
+#ifndef OAMD_C128_W4
+#define OAMD_C128_W4 1
+#endif
+static std::atomic<int> g_c128_w4{OAMD_C128_W4};
+void resnet_set_c128_four_wave(int enable) { g_c128_w4.store(enable != 0, std::memory_order_relaxed); }
+int resnet_c128_four_wave() { return g_c128_w4.load(std::memory_order_relaxed); }
+
 template <int IN>
 static void dispatch(const NetView& N, const void* feat, int fw, int H, const RowMap& M, float* pol, float* val,
                      hipStream_t s, int max_wgs = 0) {
@@ -1382,6 +1496,9 @@ static void dispatch(const NetView& N, const void* feat, int fw, int H, const Ro
         if (small) {
             if (fp16) launch_t<GeoS<128>, OAMD_FP16, IN>(N, feat, fw, H, M, pol, val, s, max_wgs);
             else launch_t<GeoS<128>, OAMD_BF16, IN>(N, feat, fw, H, M, pol, val, s, max_wgs);
+        } else if (resnet_c128_four_wave()) {
+            if (fp16) launch_t<GeoW4, OAMD_FP16, IN>(N, feat, fw, H, M, pol, val, s, max_wgs);
+            else launch_t<GeoW4, OAMD_BF16, IN>(N, feat, fw, H, M, pol, val, s, max_wgs);
         } else {
             if (fp16) launch_t<Geo<128>, OAMD_FP16, IN>(N, feat, fw, H, M, pol, val, s, max_wgs);
             else launch_t<Geo<128>, OAMD_BF16, IN>(N, feat, fw, H, M, pol, val, s, max_wgs);

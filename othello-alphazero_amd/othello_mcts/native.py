@@ -44,7 +44,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from ._othello_mcts_impl import _Net
+from ._othello_mcts_impl import _Net, resnet_c128_four_wave, set_resnet_c128_four_wave
 from .synthetic import net_config_from_state_dict
 
 _DTYPES = {"bf16": 0, "bfloat16": 0, "fp16": 1, "float16": 1}
@@ -138,6 +138,22 @@ class NativeNet:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._net.forward(x.data_ptr(), rows, policy.data_ptr(), value.data_ptr(), stream)
         return {"policy": policy, "value": value}
+
+
+def set_c128_four_wave(enable: bool) -> bool:
+    """Experimental scheduling knob (include/othello_mcts_amd_experimental.h,
+    oamd_set_resnet_c128_four_wave), process-wide: evaluate C=128 launches of
+    1024 rows or more on the 4-wave register-queue geometry of the fused kernel
+    (True) or on the 8-wave weight-ring geometry (False). Outputs are
+    bit-identical. Returns the previous setting."""
+    old = resnet_c128_four_wave()
+    set_resnet_c128_four_wave(bool(enable))
+    return old
+
+
+def c128_four_wave() -> bool:
+    """The current setting of set_c128_four_wave."""
+    return resnet_c128_four_wave()
 
 
 FP16_MAX = 65504.0

@@ -6,7 +6,8 @@ Env: ROWS (default 4096), NN_C (128 -> 128x10b, 256 -> 256x20b), NN_BLOCKS
 (conv block + residual blocks, default 10 / 20), NN_NET (torch-default
 [default], live, frontier, selfplay: bench.py bench_state_dict), NN_REAL=1
 (planes of real positions instead of random binary planes), NN_DTYPE
-(bf16 / fp16), AB_REF (save the outputs there on the first call, compare bit
+(bf16 / fp16), NN_FOUR_WAVE (C=128 throughput geometry: 1 = 4 waves, 0 = 8 waves),
+AB_REF (save the outputs there on the first call, compare bit
 for bit on later ones), CHECK_REF=1 (max error of the first 256 rows against
 the fp32 restatement oracle/resnet_ref.py; test infrastructure, diagnostics).
 Prints one line: ms per launch (median of 5 x 10 launches), TFLOP/s."""
@@ -30,6 +31,8 @@ R = int(os.environ.get("NN_BLOCKS", "10" if C == 128 else "20")) - 1
 kind = os.environ.get("NN_NET", "torch-default")
 sd = alphazero_state_dict(1, 17, C, R, C) if kind == "torch-default" else bench_state_dict(kind, 2025, 17, C, R, C)
 net = om.NativeNet(sd, device=0, dtype=dtype)
+if os.environ.get("NN_FOUR_WAVE"):  # C=128: 1 = k_resnet_w4, 0 = k_resnet_w8 (default: the build's)
+    om.native.set_c128_four_wave(os.environ["NN_FOUR_WAVE"] != "0")
 flops = 2.0 * 64 * 9 * C * (17 + 2 * R * C) + 2.0 * (64 * C * 3 + 128 * 65 + 64 * C + C)  # bench.py
 if os.environ.get("NN_REAL"):
     x = torch.from_numpy(calibration_features(rows, 8, 7)).cuda()
