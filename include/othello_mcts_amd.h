@@ -477,6 +477,36 @@ int oamd_host_solve_endgame(const oamd_position *pos_host, int32_t max_empties, 
                             int32_t *move_scores65, int32_t *score, int32_t *best_action,
                             int32_t *flags, int64_t *nodes);
 
+/* The split solver (opt-in): the same positions, outputs, flags and limits
+ * checks, another algorithm. The work item is one move of the position R one
+ * ply below a root action a (Q = the position after a; R = Q, or Q after a
+ * pass when Q's mover has none), searched with fastest-first move ordering at
+ * nodes with at least 6 empties. Phase A searches one move of R exactly,
+ * phase B the others in parallel with its value as the lower bound; two item
+ * launches between a planning and a reducing kernel. Scores, best_action and
+ * flags equal oamd_solve_endgames' wherever no node limit binds. nodes differ:
+ * per root action 1 for Q, 1 more when Q's mover passes, plus the positions
+ * its items visited; node_limit is a budget per item, and a root action with
+ * an item over it gets OAMD_SOLVE_NONE and flags the position. The workspace
+ * is the caller's, oamd_solve_split_workspace_bytes(n). Enqueued only. */
+int oamd_solve_split_workspace_bytes(int64_t n, int64_t *bytes);
+int oamd_solve_endgames_split(int32_t device, const oamd_position *pos_dev, int64_t n, int32_t max_empties,
+                              int64_t node_limit, int32_t *move_scores_dev, int32_t *score_dev,
+                              int32_t *best_action_dev, int32_t *flags_dev, int64_t *nodes_dev,
+                              void *workspace_dev, void *stream);
+/* The split solver on the host for one position: the same source, the same
+ * outputs and node counts as the device. */
+int oamd_host_solve_endgame_split(const oamd_position *pos_host, int32_t max_empties, int64_t node_limit,
+                                  int32_t *move_scores65, int32_t *score, int32_t *best_action,
+                                  int32_t *flags, int64_t *nodes);
+/* oamd_replay_relabel_endgames with the split solver between the same list
+ * and apply kernels; workspace from oamd_replay_relabel_split_workspace_bytes. */
+int oamd_replay_relabel_split_workspace_bytes(int64_t budget, int64_t *bytes);
+int oamd_replay_relabel_endgames_split(const oamd_replay_view *view, int8_t *exact_dev,
+                                       int64_t *relabel_counters_dev, int32_t max_empties, int64_t budget,
+                                       int64_t node_limit, int32_t policy_mode, int32_t retry, void *workspace_dev,
+                                       void *stream);
+
 /* Timing accumulated over the timed oamd_engine_search calls (HIP events on
  * the launching streams; a query waits for the searches still in flight):
  * total ms spent in the NN kernel, number of NN launches, rows launched

@@ -117,6 +117,11 @@ int oamd_solve_endgames_grid(int32_t device, const oamd_position *pos_dev, int64
                              int64_t node_limit, int32_t *move_scores_dev, int32_t *score_dev,
                              int32_t *best_action_dev, int32_t *flags_dev, int64_t *nodes_dev,
                              void *workspace_dev, int32_t workgroups, void *stream);
+/* The same for oamd_solve_endgames_split: both item launches use that grid. */
+int oamd_solve_endgames_split_grid(int32_t device, const oamd_position *pos_dev, int64_t n, int32_t max_empties,
+                                   int64_t node_limit, int32_t *move_scores_dev, int32_t *score_dev,
+                                   int32_t *best_action_dev, int32_t *flags_dev, int64_t *nodes_dev,
+                                   void *workspace_dev, int32_t workgroups, void *stream);
 
 #ifdef __cplusplus
 }

@@ -50,7 +50,8 @@ UNITS = {
                                  "-mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-sched-strategy=max-ilp").split()
     + ["-Rpass-analysis=kernel-resource-usage"],
     # exact endgame solver: integer code; its searcher stacks are LDS, and the
-    # build fails if the solve kernel reports any scratch (check_solver_scratch)
+    # build fails if a search kernel (k_solve, k_solve_items) reports any
+    # scratch (check_solver_scratch)
     "solver.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
@@ -90,11 +91,14 @@ def kernel_remarks(remarks: str):
 
 
 def check_solver_scratch(remarks: str) -> None:
-    """solver.hip: k_solve's searcher stacks live in LDS; a runtime-indexed
-    per-thread array would land in scratch. Fail if k_solve reports any."""
+    """solver.hip: the searcher stacks of k_solve and of the split solver's
+    item kernel k_solve_items live in LDS; a runtime-indexed per-thread array
+    would land in scratch. Fail if either search kernel reports any (the
+    planning and reducing kernels hold no stack and are not checked)."""
     seen = 0
     for name, field, value in kernel_remarks(remarks):
-        if "k_solve" in name and "reduce" not in name and field.startswith("ScratchSize"):
+        search = "k_solve" in name and "reduce" not in name and "plan" not in name
+        if search and field.startswith("ScratchSize"):
             seen += 1
             if int(value.split()[0]) != 0:
                 raise SystemExit(f"build failed: {name} uses {value} bytes of scratch per lane: "

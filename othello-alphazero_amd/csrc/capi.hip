@@ -2050,7 +2050,7 @@ int oamd_solve_workspace_bytes(int64_t n, int64_t* bytes) {
 static int solve_endgames(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
                           int64_t node_limit, int32_t* move_scores_dev, int32_t* score_dev, int32_t* best_action_dev,
                           int32_t* flags_dev, int64_t* nodes_dev, void* workspace_dev, int32_t workgroups,
-                          void* stream) {
+                          void* stream, bool split = false) {
     static_assert(sizeof(oamd_position) == 40, "layout");
     if (int rc = solve_limit_checks(max_empties, node_limit)) return rc;
     if (n < 0 || n > INT32_MAX / 65)
@@ -2065,8 +2065,9 @@ static int solve_endgames(int32_t device, const oamd_position* pos_dev, int64_t 
     DeviceGuard dg(device);
     int cus = 0;
     HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    launch_solve(pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev, best_action_dev, flags_dev,
-                 nodes_dev, workspace_dev, workgroups, cus > 0 ? cus : 1, (hipStream_t)stream);
+    (split ? launch_solve_split : launch_solve)(pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev,
+                                                best_action_dev, flags_dev, nodes_dev, workspace_dev, workgroups,
+                                                cus > 0 ? cus : 1, (hipStream_t)stream);
     LAUNCHCHK();
     return OAMD_OK;
 }
@@ -2098,6 +2099,44 @@ int oamd_host_solve_endgame(const oamd_position* pos_host, int32_t max_empties, 
     return OAMD_OK;
 }
 
+// The split solver: the same checks and outputs, its own workspace.
+int oamd_solve_split_workspace_bytes(int64_t n, int64_t* bytes) {
+    if (!bytes) return fail(OAMD_INVALID_ARGUMENT, "solve: bytes is NULL");
+    if (n < 0 || n > INT32_MAX / 65)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= n <= " + std::to_string(INT32_MAX / 65) + ", but got " +
+                                               std::to_string(n) + ".");
+    *bytes = solve_split_workspace_bytes(n);
+    return OAMD_OK;
+}
+
+int oamd_solve_endgames_split(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
+                              int64_t node_limit, int32_t* move_scores_dev, int32_t* score_dev,
+                              int32_t* best_action_dev, int32_t* flags_dev, int64_t* nodes_dev, void* workspace_dev,
+                              void* stream) {
+    return solve_endgames(device, pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev, best_action_dev,
+                          flags_dev, nodes_dev, workspace_dev, 0, stream, true);
+}
+
+int oamd_solve_endgames_split_grid(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
+                                   int64_t node_limit, int32_t* move_scores_dev, int32_t* score_dev,
+                                   int32_t* best_action_dev, int32_t* flags_dev, int64_t* nodes_dev,
+                                   void* workspace_dev, int32_t workgroups, void* stream) {
+    if (workgroups < 1)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected workgroups >= 1, but got " + std::to_string(workgroups) + ".");
+    return solve_endgames(device, pos_dev, n, max_empties, node_limit, move_scores_dev, score_dev, best_action_dev,
+                          flags_dev, nodes_dev, workspace_dev, workgroups, stream, true);
+}
+
+int oamd_host_solve_endgame_split(const oamd_position* pos_host, int32_t max_empties, int64_t node_limit,
+                                  int32_t* move_scores65, int32_t* score, int32_t* best_action, int32_t* flags,
+                                  int64_t* nodes) {
+    if (int rc = solve_limit_checks(max_empties, node_limit)) return rc;
+    if (!pos_host || !move_scores65) return fail(OAMD_INVALID_ARGUMENT, "solve: position and move_scores are required");
+    solve_host_split(pos_host->player, pos_host->player1_discs, pos_host->player2_discs, max_empties, node_limit,
+                     move_scores65, score, best_action, flags, nodes);
+    return OAMD_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Exact endgame value targets of the packed replay buffer (replay.hip + solver.hip)
 // ---------------------------------------------------------------------------
@@ -2117,9 +2156,16 @@ int oamd_replay_relabel_workspace_bytes(int64_t budget, int64_t* bytes) {
     return OAMD_OK;
 }
 
-int oamd_replay_relabel_endgames(const oamd_replay_view* view, int8_t* exact_dev, int64_t* relabel_counters_dev,
-                                 int32_t max_empties, int64_t budget, int64_t node_limit, int32_t policy_mode,
-                                 int32_t retry, void* workspace_dev, void* stream) {
+int oamd_replay_relabel_split_workspace_bytes(int64_t budget, int64_t* bytes) {
+    if (!bytes) return fail(OAMD_INVALID_ARGUMENT, "replay: bytes is NULL");
+    if (int rc = relabel_budget_check(budget)) return rc;
+    *bytes = relabel_workspace_bytes(budget, true);
+    return OAMD_OK;
+}
+
+static int replay_relabel(const oamd_replay_view* view, int8_t* exact_dev, int64_t* relabel_counters_dev,
+                          int32_t max_empties, int64_t budget, int64_t node_limit, int32_t policy_mode, int32_t retry,
+                          void* workspace_dev, void* stream, bool split) {
     if (int rc = solve_limit_checks(max_empties, node_limit)) return rc;
     if (int rc = relabel_budget_check(budget)) return rc;
     if (policy_mode != OAMD_REPLAY_POLICY_KEEP && policy_mode != OAMD_REPLAY_POLICY_OPTIMAL)
@@ -2134,9 +2180,23 @@ int oamd_replay_relabel_endgames(const oamd_replay_view* view, int8_t* exact_dev
     int cus = 0;
     HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, view->device));
     launch_replay_relabel(*view, exact_dev, relabel_counters_dev, max_empties, budget, node_limit, policy_mode,
-                          retry != 0, workspace_dev, cus > 0 ? cus : 1, (hipStream_t)stream);
+                          retry != 0, workspace_dev, cus > 0 ? cus : 1, (hipStream_t)stream, split);
     LAUNCHCHK();
     return OAMD_OK;
+}
+
+int oamd_replay_relabel_endgames(const oamd_replay_view* view, int8_t* exact_dev, int64_t* relabel_counters_dev,
+                                 int32_t max_empties, int64_t budget, int64_t node_limit, int32_t policy_mode,
+                                 int32_t retry, void* workspace_dev, void* stream) {
+    return replay_relabel(view, exact_dev, relabel_counters_dev, max_empties, budget, node_limit, policy_mode, retry,
+                          workspace_dev, stream, false);
+}
+
+int oamd_replay_relabel_endgames_split(const oamd_replay_view* view, int8_t* exact_dev, int64_t* relabel_counters_dev,
+                                       int32_t max_empties, int64_t budget, int64_t node_limit, int32_t policy_mode,
+                                       int32_t retry, void* workspace_dev, void* stream) {
+    return replay_relabel(view, exact_dev, relabel_counters_dev, max_empties, budget, node_limit, policy_mode, retry,
+                          workspace_dev, stream, true);
 }
 
 }  // extern "C"

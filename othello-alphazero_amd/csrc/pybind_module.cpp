@@ -803,6 +803,16 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                                                     reinterpret_cast<void*>(workspace),
                                                     reinterpret_cast<void*>(stream)));
              })
+        .def("relabel_split",
+             [](const oamd_replay_view& v, uintptr_t exact, uintptr_t relabel_counters, int max_empties,
+                int64_t budget, int64_t node_limit, int policy_mode, bool retry, uintptr_t workspace,
+                uintptr_t stream) {
+                 check(oamd_replay_relabel_endgames_split(&v, reinterpret_cast<int8_t*>(exact),
+                                                          reinterpret_cast<int64_t*>(relabel_counters), max_empties,
+                                                          budget, node_limit, policy_mode, retry ? 1 : 0,
+                                                          reinterpret_cast<void*>(workspace),
+                                                          reinterpret_cast<void*>(stream)));
+             })
         .def("gather",
              [](const oamd_replay_view& v, uintptr_t ids, int64_t n, uintptr_t feat, uintptr_t pol, uintptr_t val,
                 uintptr_t stream) {
@@ -827,6 +837,26 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
         int64_t nodes = 0;
         check(oamd_host_solve_endgame(&p, max_empties, node_limit, ms, &score, &best, &flags, &nodes));
         return py::make_tuple(std::vector<int>(ms, ms + 65), score, best, flags, nodes);
+    });
+    m.def("_host_solve_split", [](int player, uint64_t p1, uint64_t p2, int max_empties, int64_t node_limit) {
+        oamd_position p{};
+        p.player = player;
+        p.player1_discs = p1;
+        p.player2_discs = p2;
+        int32_t ms[65], score = 0, best = 0, flags = 0;
+        int64_t nodes = 0;
+        check(oamd_host_solve_endgame_split(&p, max_empties, node_limit, ms, &score, &best, &flags, &nodes));
+        return py::make_tuple(std::vector<int>(ms, ms + 65), score, best, flags, nodes);
+    });
+    m.def("_relabel_split_workspace_bytes", [](int64_t budget) {
+        int64_t bytes = 0;
+        check(oamd_replay_relabel_split_workspace_bytes(budget, &bytes));
+        return bytes;
+    });
+    m.def("_solve_split_workspace_bytes", [](int64_t n) {
+        int64_t bytes = 0;
+        check(oamd_solve_split_workspace_bytes(n, &bytes));
+        return bytes;
     });
     m.def("_relabel_workspace_bytes", [](int64_t budget) {
         int64_t bytes = 0;
@@ -855,6 +885,25 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
         else
             check(oamd_solve_endgames_grid(device, P, n, max_empties, node_limit, ms, sc, be, fl, no, ws, workgroups,
                                            st));
+    });
+
+    // the split solver: the same convention
+    m.def("_gpu_solve_split", [](int device, uintptr_t pos, int64_t n, int max_empties, int64_t node_limit,
+                                 uintptr_t move_scores, uintptr_t score, uintptr_t best, uintptr_t flags,
+                                 uintptr_t nodes, uintptr_t workspace, int workgroups, uintptr_t stream) {
+        auto* P = reinterpret_cast<const oamd_position*>(pos);
+        auto* ms = reinterpret_cast<int32_t*>(move_scores);
+        auto* sc = reinterpret_cast<int32_t*>(score);
+        auto* be = reinterpret_cast<int32_t*>(best);
+        auto* fl = reinterpret_cast<int32_t*>(flags);
+        auto* no = reinterpret_cast<int64_t*>(nodes);
+        void* ws = reinterpret_cast<void*>(workspace);
+        void* st = reinterpret_cast<void*>(stream);
+        if (workgroups == 0)
+            check(oamd_solve_endgames_split(device, P, n, max_empties, node_limit, ms, sc, be, fl, no, ws, st));
+        else
+            check(oamd_solve_endgames_split_grid(device, P, n, max_empties, node_limit, ms, sc, be, fl, no, ws,
+                                                 workgroups, st));
     });
 
     // GPU bitboard kernels over device buffers (data_ptr ints) for parity tests

@@ -28,16 +28,17 @@ void launch_replay_gather(const oamd_replay_view& V, const int64_t* ids, int64_t
 
 
 // The caller's relabel workspace for `budget` list rows, widest alignment
-// first: the solver's own workspace, the position list, then the int32 arrays
-// (slot list, move_scores, score, best_action, flags).
+// first: the solver's own workspace (the split solver's when `split`), the
+// position list, then the int32 arrays (slot list, move_scores, score,
+// best_action, flags).
 struct RelabelWorkspace {
     void* solver;
     oamd_position* pos;
     int32_t *slots, *move_scores, *score, *best_action, *flags;
-    RelabelWorkspace(void* base, int64_t budget) {
+    RelabelWorkspace(void* base, int64_t budget, bool split = false) {
         char* p = static_cast<char*>(base);
         solver = p;
-        p += solve_workspace_bytes(budget);
+        p += split ? solve_split_workspace_bytes(budget) : solve_workspace_bytes(budget);
         pos = reinterpret_cast<oamd_position*>(p);
         p += budget * (int64_t)sizeof(oamd_position);
         slots = reinterpret_cast<int32_t*>(p);
@@ -47,14 +48,16 @@ struct RelabelWorkspace {
         flags = best_action + budget;
     }
 };
-inline int64_t relabel_workspace_bytes(int64_t budget) {
-    return solve_workspace_bytes(budget) + budget * (int64_t)(sizeof(oamd_position) + (1 + 65 + 3) * sizeof(int32_t));
+inline int64_t relabel_workspace_bytes(int64_t budget, bool split = false) {
+    return (split ? solve_split_workspace_bytes(budget) : solve_workspace_bytes(budget)) +
+           budget * (int64_t)(sizeof(oamd_position) + (1 + 65 + 3) * sizeof(int32_t));
 }
 // Exact value targets for the ring's last plies: list the candidates (live
 // positions in age order, at most `budget`), solve them, apply the answers
-// (list kernel, launch_solve, apply kernel; stream order).
+// (list kernel, launch_solve or with `split` launch_solve_split, apply kernel;
+// stream order).
 void launch_replay_relabel(const oamd_replay_view& V, int8_t* exact, int64_t* relabel_counters, int32_t max_empties,
                            int64_t budget, int64_t node_limit, int32_t policy_mode, int32_t retry, void* workspace,
-                           int32_t compute_units, hipStream_t s);
+                           int32_t compute_units, hipStream_t s, bool split = false);
 
 }  // namespace oamd

@@ -369,12 +369,12 @@ void launch_replay_add(const oamd_replay_view& V, int8_t* exact, const int32_t* 
 
 void launch_replay_relabel(const oamd_replay_view& V, int8_t* exact, int64_t* relabel_counters, int32_t max_empties,
                            int64_t budget, int64_t node_limit, int32_t policy_mode, int32_t retry, void* workspace,
-                           int32_t compute_units, hipStream_t s) {
-    const RelabelWorkspace w(workspace, budget);
+                           int32_t compute_units, hipStream_t s, bool split) {
+    const RelabelWorkspace w(workspace, budget, split);
     hipLaunchKernelGGL(k_replay_endgame_list, dim3(1), dim3(kCommitThreads), 0, s, V, exact, relabel_counters,
                        max_empties, budget, retry, w.pos, w.slots);
-    launch_solve(w.pos, budget, max_empties, node_limit, w.move_scores, w.score, w.best_action, w.flags, nullptr,
-                 w.solver, 0, compute_units, s);
+    (split ? launch_solve_split : launch_solve)(w.pos, budget, max_empties, node_limit, w.move_scores, w.score,
+                                                w.best_action, w.flags, nullptr, w.solver, 0, compute_units, s);
     const unsigned blocks = (unsigned)((budget + kGatherWaves - 1) / kGatherWaves);
     hipLaunchKernelGGL(k_replay_endgame_apply, dim3(blocks), dim3(64 * kGatherWaves), 0, s, V, exact,
                        relabel_counters, budget, policy_mode, w.slots, w.move_scores, w.score, w.best_action, w.flags);

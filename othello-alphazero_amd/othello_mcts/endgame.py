@@ -12,6 +12,13 @@ move is terminal: ``score`` = black minus white, ``best_action`` = -1.
 It stands in for the external engine behind the reference's ``EgaroucidPlayer``
 (player.py:262-321) as an absolute yardstick: ``endgame_move_loss`` says how
 many discs a move gave away against perfect play.
+
+``split=True`` selects the split solver: the work item is one
+move of the position one ply below a root action, searched with fastest-first
+move ordering, in two phases. Scores, ``best_action`` and flags are the same
+wherever no node limit binds; ``nodes`` are fewer and counted per item (1 for
+the position after the root action, 1 more when its mover passes, plus the
+items), and ``node_limit`` is a budget per item.
 """
 
 from __future__ import annotations
@@ -21,7 +28,8 @@ from typing import Sequence
 
 import torch
 
-from ._othello_mcts_impl import Position, _gpu_solve, _host_solve, _solve_workspace_bytes
+from ._othello_mcts_impl import (Position, _gpu_solve, _gpu_solve_split, _host_solve, _host_solve_split,
+                                 _solve_split_workspace_bytes, _solve_workspace_bytes)
 
 NONE = -128
 # per-position flags (include/othello_mcts_amd.h OAMD_SOLVE_*)
@@ -94,15 +102,17 @@ def random_play_positions(empties: int, count: int, seed: int) -> list[Position]
     return out
 
 
-def solve_position(position, max_empties: int = 12, node_limit: int = DEFAULT_NODE_LIMIT) -> dict:
+def solve_position(position, max_empties: int = 12, node_limit: int = DEFAULT_NODE_LIMIT, split: bool = False) -> dict:
     """The host solver for one ``Position`` (or ``(player, player1_discs,
     player2_discs)``); needs no GPU. Returns ``move_scores`` (65 ints),
-    ``score``, ``best_action``, ``flags`` and ``nodes``."""
+    ``score``, ``best_action``, ``flags`` and ``nodes``. ``split``: the split
+    solver's host twin."""
     _check_limits(max_empties, node_limit)
     player, p1, p2 = _fields(position)
     if not -(1 << 31) <= player < 1 << 31:
         raise ValueError(f"Expected player as an int32, but got {player}.")
-    ms, score, best, flags, nodes = _host_solve(player, p1, p2, max_empties, node_limit)
+    ms, score, best, flags, nodes = (_host_solve_split if split else _host_solve)(player, p1, p2, max_empties,
+                                                                                  node_limit)
     return {"move_scores": ms, "score": score, "best_action": best, "flags": flags, "nodes": nodes}
 
 
@@ -129,14 +139,14 @@ class EndgameSolution:
 
 
 def solve_endgames(positions, max_empties: int = 12, node_limit: int = DEFAULT_NODE_LIMIT,
-                   _workgroups: int = 0) -> EndgameSolution:
+                   _workgroups: int = 0, split: bool = False) -> EndgameSolution:
     """Solve n positions on the GPU. ``positions``: an ``(n, 5)`` int64 device
     tensor in ``oamd_position`` layout (``BatchedMCTS.root_positions()``), or a
     sequence of ``Position`` objects / ``(player, player1_discs,
     player2_discs)`` triples, packed and uploaded to the current device.
     Enqueued on the current torch stream; nothing waits on the host.
     ``_workgroups`` (tests): that many 64-lane workgroups instead of the
-    chip-filling grid; no output depends on it."""
+    chip-filling grid; no output depends on it. ``split``: the split solver."""
     _check_limits(max_empties, node_limit)
     if isinstance(positions, torch.Tensor):
         pos = positions
@@ -161,26 +171,29 @@ def solve_endgames(positions, max_empties: int = 12, node_limit: int = DEFAULT_N
                           torch.empty((n,), dtype=torch.int64, device=d))
     if n == 0:
         return sol
-    ws = torch.empty((_solve_workspace_bytes(n),), dtype=torch.uint8, device=d)
-    _gpu_solve(d.index, pos.data_ptr(), n, max_empties, node_limit, sol.move_scores.data_ptr(), sol.score.data_ptr(),
-               sol.best_action.data_ptr(), sol.flags.data_ptr(), sol.nodes.data_ptr(), ws.data_ptr(), _workgroups,
-               torch.cuda.current_stream(d).cuda_stream)
+    workspace_bytes, solve = (_solve_split_workspace_bytes, _gpu_solve_split) if split else \
+        (_solve_workspace_bytes, _gpu_solve)
+    ws = torch.empty((workspace_bytes(n),), dtype=torch.uint8, device=d)
+    solve(d.index, pos.data_ptr(), n, max_empties, node_limit, sol.move_scores.data_ptr(), sol.score.data_ptr(),
+          sol.best_action.data_ptr(), sol.flags.data_ptr(), sol.nodes.data_ptr(), ws.data_ptr(), _workgroups,
+          torch.cuda.current_stream(d).cuda_stream)
     # the caching allocator hands a freed block to later work of the same stream only
     return sol
 
 
 def endgame_move_loss(roots: torch.Tensor, actions: torch.Tensor, max_empties: int = 12,
-                      node_limit: int = DEFAULT_NODE_LIMIT, solution: EndgameSolution | None = None
-                      ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                      node_limit: int = DEFAULT_NODE_LIMIT, solution: EndgameSolution | None = None,
+                      split: bool = False) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """How far the moves ``actions`` (G) played from ``roots`` (G, 5) are from
     perfect play: ``(loss, wdl_kept, empties)``, device tensors of length G.
     ``loss = score - move_scores[action] >= 0`` discs given away, ``wdl_kept``
     = 1 where the move keeps the sign of the exact result, else 0. Both are -1
     where the root has more than ``max_empties`` empties, is terminal, was not
     solved, or ``action < 0``. ``solution``: the roots' solution if the caller
-    has it already. No host wait."""
+    has it already; otherwise the roots are solved here, by the split solver
+    with ``split``. No host wait."""
     if solution is None:
-        solution = solve_endgames(roots, max_empties, node_limit)
+        solution = solve_endgames(roots, max_empties, node_limit, split=split)
     d = roots.device
     a = actions.to(d, torch.int64).reshape(-1)
     if a.shape[0] != roots.shape[0]:

@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import torch
 
-from ._othello_mcts_impl import _relabel_workspace_bytes, _ReplayView
+from ._othello_mcts_impl import _relabel_split_workspace_bytes, _relabel_workspace_bytes, _ReplayView
 from .endgame import DEFAULT_NODE_LIMIT, _check_limits
 
 # sticky bits of the device counter block (include/othello_mcts_amd.h OAMD_REPLAY_*)
@@ -127,6 +127,7 @@ class ReplayBuffer:
             # labelled so far, given up so far, left behind by the last call, taken by the last call
             self.relabel_counters = torch.zeros((4,), dtype=torch.int64, device=d)
             self._relabel_ws: dict[int, torch.Tensor] = {}  # workspace per budget
+            self._relabel_split_ws: dict[int, torch.Tensor] = {}  # the split solver's, per budget
 
     # ------------------------------------------------------------------ plumbing
     def _view(self) -> _ReplayView:
@@ -170,23 +171,29 @@ class ReplayBuffer:
 
     # ------------------------------------------------------------------ exact endgame targets
     def relabel_endgames(self, max_empties: int = 10, budget: int = 4096, node_limit: int = DEFAULT_NODE_LIMIT,
-                         policy: str = "keep", retry: bool = False) -> None:
+                         policy: str = "keep", retry: bool = False, split: bool = False) -> None:
         """Give the live positions with at most ``max_empties`` empties their
         exact value target: the sign of the result of perfect play for the side
         to move, from ``solve_endgames``' kernels. Oldest first, at most
         ``budget`` positions per call; a position is examined once (again with
         ``retry`` if the solver gave up on it: ``node_limit``, an invalid
         record). ``policy="optimal"`` also replaces the policy row by the
-        uniform distribution over the optimal actions. Enqueues only."""
+        uniform distribution over the optimal actions. ``split``: solve with the
+        split solver (``solve_endgames(split=True)``; ``node_limit`` is then a
+        budget per item). Enqueues only."""
         _check_relabel(max_empties, budget, node_limit, policy, retry)
         if not self.track_exact:
             raise RuntimeError("ReplayBuffer.relabel_endgames needs a buffer created with track_exact=True.")
-        ws = self._relabel_ws.get(budget)
+        cache, workspace_bytes = (self._relabel_split_ws, _relabel_split_workspace_bytes) if split else \
+            (self._relabel_ws, _relabel_workspace_bytes)
+        ws = cache.get(budget)
         if ws is None:
-            ws = torch.empty((_relabel_workspace_bytes(budget),), dtype=torch.uint8, device=self.device)
-            self._relabel_ws[budget] = ws
-        self._view().relabel(self.exact.data_ptr(), self.relabel_counters.data_ptr(), max_empties, budget, node_limit,
-                             _POLICY_MODES[policy], retry, ws.data_ptr(), self._stream())
+            ws = torch.empty((workspace_bytes(budget),), dtype=torch.uint8, device=self.device)
+            cache[budget] = ws
+        view = self._view()
+        relabel = view.relabel_split if split else view.relabel
+        relabel(self.exact.data_ptr(), self.relabel_counters.data_ptr(), max_empties, budget, node_limit,
+                _POLICY_MODES[policy], retry, ws.data_ptr(), self._stream())
 
     @property
     def relabel_stats(self) -> dict[str, int]:

@@ -59,6 +59,7 @@ def main() -> None:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--node-limit", type=int, default=om.endgame.DEFAULT_NODE_LIMIT)
+    ap.add_argument("--split", action="store_true", help="solve with the split solver (DESIGN.md §15)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
 
@@ -78,7 +79,7 @@ def main() -> None:
             roots = b.root_positions()
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            sol = om.solve_endgames(roots, E, a.node_limit)
+            sol = om.solve_endgames(roots, E, a.node_limit, split=a.split)
             t1.record()
             events.append((t0, t1))
             b.search(net, sync=False)

@@ -47,6 +47,7 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=77)
     ap.add_argument("--budget", type=int, default=16384)
     ap.add_argument("--node-limit", type=int, default=om.endgame.DEFAULT_NODE_LIMIT)
+    ap.add_argument("--split", action="store_true", help="relabel with the split solver (DESIGN.md §15)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
 
@@ -72,7 +73,7 @@ def main() -> None:
     while True:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        rb.relabel_endgames(E, a.budget, a.node_limit)
+        rb.relabel_endgames(E, a.budget, a.node_limit, split=a.split)
         t1.record()
         events.append((t0, t1))
         calls += 1

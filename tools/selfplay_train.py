@@ -12,7 +12,7 @@ trained net's are (trees of a trained net concentrate and
 descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
-Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds] [packed [exact=K]]
+Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds] [packed [exact=K [split]]]
 
 packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
 million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
@@ -23,7 +23,8 @@ exact=K (with packed): after each self-play phase and before training, the
 buffer's positions with at most K empties get the exact result of perfect play
 as their value target (ReplayBuffer.relabel_endgames). The
 iteration's log line gains relabel_ms (device events around the call) and the
-buffer's relabel_stats.
+buffer's relabel_stats. split (with exact=K): the split solver does the
+relabelling (relabel_endgames(split=True)).
 """
 
 import json
@@ -92,6 +93,9 @@ def main():
     exact = [int(w[6:]) for w in sys.argv[5:] if w.startswith("exact=")]
     if exact and not packed:
         raise SystemExit("exact=K needs the packed buffer")
+    split = "split" in sys.argv[5:]
+    if split and not exact:
+        raise SystemExit("split needs exact=K")
     moves_per_iter = 64
     torch.manual_seed(0)
     dev = torch.device("cuda", 0)
@@ -128,7 +132,7 @@ def main():
         if exact:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            buf.relabel_endgames(exact[0])
+            buf.relabel_endgames(exact[0], split=split)
             e1.record()
             stats = buf.relabel_stats  # the iteration's one host wait for the relabel
             relabel = {"relabel_ms": round(e0.elapsed_time(e1), 2), "relabel": stats}
@@ -157,7 +161,8 @@ def main():
     Path(str(out) + ".json").write_text(json.dumps({"iterations": log, "games_per_engine": G,
                                                     "moves_per_iteration": moves_per_iter,
                                                     "buffer": "packed" if packed else "fp32",
-                                                    "exact_max_empties": exact[0] if exact else None}, indent=1))
+                                                    "exact_max_empties": exact[0] if exact else None,
+                                                    "exact_split": split}, indent=1))
 
 
 if __name__ == "__main__":
