@@ -26,6 +26,12 @@ value pre-activation within +-3.
 
 forward_exact is the integer reference. It is linked to the fp32 torch
 restatement (oracle/resnet_ref.py) in tests/test_cpu_exact_nets.py.
+
+These nets avoid rounding on purpose: they prove addressing and accumulation.
+Which number the kernel's epilogue and the loader round to is pinned, with the
+same comparison, by the third family in tests/rounding_nets.py (nets whose
+layer results do not fit the 16-bit format); how large the rounding error of
+a live net is stays with the tolerance tests of tests/test_gpu_resnet.py.
 """
 
 from __future__ import annotations

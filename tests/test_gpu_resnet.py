@@ -21,8 +21,12 @@ value has std < 1e-3 and its priors sit within 0.02 nats of uniform
 (tests/test_cpu_nets.py::test_torch_default_init_is_degenerate), so exchanged
 boards, a wrong output row, a mirrored or dropped tap or two swapped channels
 pass these tolerances. Addressing and accumulation are checked without slack
-on exact-arithmetic nets in tests/test_gpu_resnet_exact.py; this file owns
-the rounding behaviour.
+on exact-arithmetic nets in tests/test_gpu_resnet_exact.py. Which number the
+epilogue and the loader round to is checked without slack too, on the
+rounding probe nets of tests/test_gpu_resnet_rounding.py: these tolerances
+cannot see a wrong rounding rule (a truncating kernel stays a factor 2 to 20
+inside LIVE_TOL on a live net). This file owns how large the rounding error
+is on a live net.
 """
 
 import json

@@ -4,8 +4,10 @@ bf16 and fp16 hold exactly, heads whose fp32 sums are exact in any order. The
 kernel must reproduce the integer reference's logits and value pre-activation
 to a quarter of the smallest change one wrong tower unit can cause, so one
 misrouted channel, tap, board, row or K-step fails the case. What the nets
-prove is addressing and accumulation, not rounding behaviour: that stays with
-the tolerance tests of tests/test_gpu_resnet.py. tests/test_cpu_exact_nets.py
+prove is addressing and accumulation, not rounding behaviour: which number
+is stored is pinned by tests/test_gpu_resnet_rounding.py, how large the
+rounding error of a live net is stays with the tolerance tests of
+tests/test_gpu_resnet.py. tests/test_cpu_exact_nets.py
 asserts the exactness conditions for exactly these cases and that the
 comparison rejects the bug classes named there. The terminal summary lists
 every case's largest deviation in steps (the limit is 0.25)."""
