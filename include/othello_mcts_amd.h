@@ -282,6 +282,36 @@ int oamd_engine_selfplay_move(oamd_engine *e, const oamd_selfplay_config *cfg,
 int oamd_engine_selfplay_steps(oamd_engine *e, oamd_net *net, const oamd_selfplay_config *cfg,
                                int32_t n_moves, int32_t per_move_outputs, int32_t *actions_dev,
                                int32_t *finished_dev, float *features_dev, float *policy_dev);
+/* Adjudication by the exact endgame solver (opt-in; the variants below with
+ * max_empties = 0 ARE the calls above). K = max_empties in 1..16: after a
+ * searched move has been applied, a new root that is not terminal and has at
+ * most K empty squares (a mover that must pass counts) ends the game there. The
+ * root is solved exactly (oamd_solve_endgames, or oamd_solve_endgames_split
+ * when split != 0, with the largest node limit) and reported like a game that
+ * ended on the board: the game restarts in the same launch, and
+ *   finished bit 5 (32) = the game was adjudicated at this move; bits 0-1 = 2,
+ *     3 or 1 for margin > 0, < 0, = 0, filled in by a resolve step the call
+ *     enqueues on the engine's stream after the moves (stream order);
+ *   finished bit 6 (64) = the solver flagged the position (no outcome bits;
+ *     cannot happen for a position the engine produced);
+ *   margin_dev (shaped like finished_dev, may be NULL): the exact score seen
+ *     from black (the solver's score, negated when white is to move), black
+ *     minus white discs for a game that ended on the board, INT32_MIN where no
+ *     game ended.
+ * The test runs only after a searched move: a restart whose random opening
+ * lands at or below K empties is searched once, then adjudicated. finished_dev
+ * is required when max_empties > 0. OAMD_INVALID_ARGUMENT: max_empties outside
+ * 0..16; max_empties > 0 with n_moves > 1 and per_move_outputs = 0 (the
+ * pending positions of a move would be overwritten by the next). The engine
+ * owns the workspace and grows it on demand. Enqueued only. */
+int oamd_engine_selfplay_move_adjudicated(oamd_engine *e, const oamd_selfplay_config *cfg,
+                                          int32_t *actions_dev, int32_t *finished_dev, float *features_dev,
+                                          float *policy_dev, int32_t max_empties, int32_t split,
+                                          int32_t *margin_dev);
+int oamd_engine_selfplay_steps_adjudicated(oamd_engine *e, oamd_net *net, const oamd_selfplay_config *cfg,
+                                           int32_t n_moves, int32_t per_move_outputs, int32_t *actions_dev,
+                                           int32_t *finished_dev, float *features_dev, float *policy_dev,
+                                           int32_t max_empties, int32_t split, int32_t *margin_dev);
 /* Reset every game to a random opening. */
 int oamd_engine_random_openings(oamd_engine *e, int32_t max_moves, uint64_t seed);
 /* The random-stream key of a game (DESIGN.md "Random streams"). */
@@ -339,6 +369,24 @@ int oamd_arena_move(oamd_engine *a, oamd_engine *b, const oamd_selfplay_config *
 int oamd_arena_play(oamd_engine *a, oamd_net *net_a, oamd_engine *b, oamd_net *net_b,
                     const oamd_selfplay_config *cfg, int32_t max_plies, int32_t *actions_dev,
                     int32_t *finished_dev, int32_t *discs_dev, int32_t *plies_host);
+/* The same with adjudication (the rule of
+ * oamd_engine_selfplay_move_adjudicated; max_empties = 0 is the call above).
+ * An adjudicated match stops: finished bit 5 is set with the outcome bits of
+ * the exact margin, neither tree stays active, remaining is decremented once,
+ * later plies report action -1, and discs_dev holds the disc counts AT the
+ * adjudicated position. margin_dev (G, may be NULL): the exact margin seen
+ * from black, black minus white for a match that ended on the board.
+ * oamd_arena_move_adjudicated writes margin_dev only for matches that end at
+ * this ply; oamd_arena_play_adjudicated writes all G entries, INT32_MIN for a
+ * match that did not end in the call. finished_dev is required when
+ * max_empties > 0. */
+int oamd_arena_move_adjudicated(oamd_engine *a, oamd_engine *b, const oamd_selfplay_config *cfg,
+                                int32_t *actions_dev, int32_t *finished_dev, int32_t *discs_dev,
+                                int32_t *remaining_dev, int32_t max_empties, int32_t split, int32_t *margin_dev);
+int oamd_arena_play_adjudicated(oamd_engine *a, oamd_net *net_a, oamd_engine *b, oamd_net *net_b,
+                                const oamd_selfplay_config *cfg, int32_t max_plies, int32_t *actions_dev,
+                                int32_t *finished_dev, int32_t *discs_dev, int32_t *plies_host,
+                                int32_t max_empties, int32_t split, int32_t *margin_dev);
 
 /* ------------------------------------------------------------------------ */
 /* Packed replay buffer: a ring of POSITIONS (2H bitboards, the side to move, */
@@ -355,6 +403,7 @@ int oamd_arena_play(oamd_engine *a, oamd_net *net_a, oamd_engine *b, oamd_net *n
 #define OAMD_REPLAY_NO_TARGETS 2 /* finished bit 2 on a played game: no targets were written */
 #define OAMD_REPLAY_TOO_LONG 4   /* a game staged more than max_moves moves */
 #define OAMD_REPLAY_BAD_ID 8     /* a gather id outside [0, 8 * size) */
+#define OAMD_REPLAY_SOLVER_FLAG 16 /* finished bit 6: the solver flagged an adjudicated position */
 
 typedef struct oamd_replay_view {
     int32_t device;       /* HIP device of every pointer below */
@@ -388,7 +437,9 @@ typedef struct oamd_replay_view {
  * outcome for black, negated where white was to move), oldest positions
  * overwritten. A row with finished bit 3, with bit 2 on a played game, or of
  * a game already holding max_moves moves sets its sticky bit instead and is
- * skipped (a game that finished in such a row is dropped). Enqueued only. */
+ * skipped (a game that finished in such a row is dropped). A row with
+ * finished bit 6 (an adjudicated game without an outcome) sets
+ * OAMD_REPLAY_SOLVER_FLAG and drops the game's staged moves. Enqueued only. */
 int oamd_replay_add(const oamd_replay_view *view, int32_t n_moves, const int32_t *actions_dev,
                     const int32_t *finished_dev, const float *features_dev, const float *policy_dev,
                     void *stream);

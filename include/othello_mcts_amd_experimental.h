@@ -123,6 +123,13 @@ int oamd_solve_endgames_split_grid(int32_t device, const oamd_position *pos_dev,
                                    int32_t *best_action_dev, int32_t *flags_dev, int64_t *nodes_dev,
                                    void *workspace_dev, int32_t workgroups, void *stream);
 
+/* Diagnostics: device time (HIP events) of the engine's last adjudication
+ * resolve step (solver + apply, oamd_engine_*_adjudicated / oamd_arena_*_adjudicated
+ * with max_empties > 0) and the number of resolve steps enqueued so far
+ * (resolves may be NULL). The first call switches the recording on: resolve
+ * steps enqueued before it are not timed (0 ms). Waits for the timed step. */
+int oamd_engine_adjudicate_ms(oamd_engine *e, float *ms, int64_t *resolves);
+
 #ifdef __cplusplus
 }
 #endif

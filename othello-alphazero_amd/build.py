@@ -1,6 +1,6 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
-  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip) + the C ABI
+  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip, adjudicate.hip) + the C ABI
                            (capi.hip),
                            hipcc --offload-arch=gfx950
   _othello_mcts_impl*.so   pybind11 host layer (pybind_module.cpp) over the C ABI
@@ -53,6 +53,8 @@ UNITS = {
     # build fails if a search kernel (k_solve, k_solve_items) reports any
     # scratch (check_solver_scratch)
     "solver.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # adjudication's apply kernel: integer code
+    "adjudicate.hip": [],
 }
 
 

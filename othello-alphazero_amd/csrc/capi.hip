@@ -181,6 +181,68 @@ int validate_config(const oamd_search_config* c) {
     return OAMD_OK;
 }
 
+// Adjudication: the pending positions of one call (one slot
+// per `finished` word, all-zero where no game ended) and what the solver needs
+// for one chunk of them. Engine-owned, grown lazily; hipFree waits for the
+// device, so growing never pulls a buffer from under queued work.
+struct AdjudicateWorkspace {
+    static constexpr int64_t kChunk = 4096;  // positions per solver launch
+    oamd_position* pending = nullptr;
+    int64_t pending_cap = 0;
+    int32_t* move_scores = nullptr;  // chunk x 65
+    int32_t* score = nullptr;        // chunk
+    int32_t* flags = nullptr;        // chunk
+    char* solve_ws = nullptr;
+    int64_t chunk_cap = 0, solve_ws_bytes = 0;
+    int cus = 0;
+    hipEvent_t ev[2] = {};  // around the last resolve step, once oamd_engine_adjudicate_ms was called
+    bool want_ms = false, timed = false;
+    int64_t resolves = 0;
+    int ensure(int device, int64_t n, bool split) {
+        if (!ev[0]) {
+            for (auto& x : ev)
+                if (hipEventCreate(&x) != hipSuccess) return fail(OAMD_RUNTIME, "adjudication: hipEventCreate failed");
+            HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+            if (cus < 1) cus = 1;
+        }
+        if (n > pending_cap) {
+            dfree(pending);
+            pending_cap = 0;
+            if (int rc = dalloc(&pending, (size_t)n)) return rc;
+            pending_cap = n;
+        }
+        const int64_t chunk = std::min<int64_t>(n, kChunk);
+        if (chunk > chunk_cap) {
+            dfree(move_scores);
+            dfree(score);
+            dfree(flags);
+            chunk_cap = 0;
+            int rc;
+            if ((rc = dalloc(&move_scores, (size_t)chunk * 65)) || (rc = dalloc(&score, (size_t)chunk)) ||
+                (rc = dalloc(&flags, (size_t)chunk)))
+                return rc;
+            chunk_cap = chunk;
+        }
+        const int64_t bytes = split ? solve_split_workspace_bytes(chunk_cap) : solve_workspace_bytes(chunk_cap);
+        if (bytes > solve_ws_bytes) {
+            dfree(solve_ws);
+            solve_ws_bytes = 0;
+            if (int rc = dalloc(&solve_ws, (size_t)bytes)) return rc;
+            solve_ws_bytes = bytes;
+        }
+        return OAMD_OK;
+    }
+    void destroy() {
+        dfree(pending);
+        dfree(move_scores);
+        dfree(score);
+        dfree(flags);
+        dfree(solve_ws);
+        for (auto x : ev)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
 }  // namespace
 
 // ===========================================================================
@@ -256,6 +318,7 @@ struct oamd_engine {
     int ensure_remaining() {
         return remaining.ensure((size_t)kMaxPipeline, (size_t)kFreeSlots * kMaxPipeline, "free-running slots");
     }
+    AdjudicateWorkspace adj;  // oamd_engine_selfplay_*_adjudicated, oamd_arena_*_adjudicated
     // workgroups of an extra round's ResNet launch (0 = the regular grid)
     int extra_grid = 128;
     int step_phase = 0;  // 1 = a selected round awaits its backup (step API)
@@ -558,6 +621,7 @@ struct oamd_engine {
         for (auto& c : span_chunks) dfree(c.p);
         cuts.destroy();
         remaining.destroy();
+        adj.destroy();
         for (int k = 0; k < n_pipe_streams; ++k) {
             (void)hipStreamDestroy(pipe_stream[k]);
             (void)hipEventDestroy(join_ev[k]);
@@ -1639,14 +1703,89 @@ static SelfplayParams selfplay_params(const oamd_selfplay_config* cfg) {
     return SelfplayParams{cfg->temperature_moves, cfg->temperature, cfg->opening_moves, cfg->emit_targets};
 }
 
-int oamd_engine_selfplay_move(oamd_engine* e, const oamd_selfplay_config* cfg, int32_t* actions_dev,
-                              int32_t* finished_dev, float* features_dev, float* policy_dev) {
-    if (int rc = selfplay_cfg_checks(cfg, features_dev, policy_dev)) return rc;
-    DeviceGuard dg(e->device);
-    launch_selfplay_move(e->view(), selfplay_params(cfg), 0, e->G, actions_dev, finished_dev, features_dev, policy_dev,
-                         e->stream);
+// ---------------------------------------------------------------------------
+// Adjudication by the exact solver. A call zeroes its pending
+// slots on the caller's stream before the moves (adjudicate_begin), the move
+// kernels mark them (tree.hip), and the resolve step, on the caller's stream
+// after every group has joined, solves them and writes the outcome bits and
+// the margins (adjudicate.hip). Everything is enqueued only.
+// ---------------------------------------------------------------------------
+static int adjudicate_checks(int32_t max_empties, const int32_t* finished_dev) {
+    if (max_empties < 0 || max_empties > kSolveMaxEmpties)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= max_empties <= " + std::to_string(kSolveMaxEmpties) +
+                                               ", but got " + std::to_string(max_empties) + ".");
+    if (max_empties > 0 && !finished_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "adjudication needs the finished buffer");
+    return OAMD_OK;
+}
+
+// n pending slots, zeroed; sp gets the adjudication fields
+static int adjudicate_begin(oamd_engine* e, int64_t n, int32_t max_empties, bool split, SelfplayParams* sp) {
+    if (n <= 0) return OAMD_OK;
+    if (int rc = e->adj.ensure(e->device, n, split)) return rc;
+    HIPCHK(hipMemsetAsync(e->adj.pending, 0, sizeof(oamd_position) * (size_t)n, e->stream));
+    sp->adj_empties = max_empties;
+    sp->adj_pending = e->adj.pending;
+    return OAMD_OK;
+}
+
+// accumulate: the arena's cumulative words (only ended matches are touched)
+static int adjudicate_resolve(oamd_engine* e, int64_t n, int32_t max_empties, bool split, int32_t* finished_dev,
+                              int32_t* margin_dev, bool accumulate) {
+    if (n <= 0) return OAMD_OK;
+    AdjudicateWorkspace& w = e->adj;
+    constexpr int64_t kNoLimit = (1LL << kSolveStatusShift) - 1;  // <= 16 empties: the solver always finishes
+    if (w.want_ms) HIPCHK(hipEventRecord(w.ev[0], e->stream));
+    for (int64_t c0 = 0; c0 < n; c0 += w.chunk_cap) {
+        const int64_t nc = std::min<int64_t>(w.chunk_cap, n - c0);
+        (split ? launch_solve_split : launch_solve)(w.pending + c0, nc, max_empties, kNoLimit, w.move_scores, w.score,
+                                                    nullptr, w.flags, nullptr, w.solve_ws, 0, w.cus, e->stream);
+        launch_adjudicate_apply(w.pending + c0, w.score, w.flags, nc, finished_dev + c0,
+                                margin_dev ? margin_dev + c0 : nullptr, accumulate ? 1 : 0, e->stream);
+    }
+    if (w.want_ms) HIPCHK(hipEventRecord(w.ev[1], e->stream));
+    w.timed = w.want_ms;
+    ++w.resolves;
     LAUNCHCHK();
     return OAMD_OK;
+}
+
+int oamd_engine_adjudicate_ms(oamd_engine* e, float* ms, int64_t* resolves) {
+    if (!ms) return fail(OAMD_INVALID_ARGUMENT, "adjudication: ms is NULL");
+    *ms = 0.0f;
+    if (resolves) *resolves = e->adj.resolves;
+    e->adj.want_ms = true;  // the resolve steps from here on record their events
+    if (!e->adj.timed) return OAMD_OK;
+    DeviceGuard dg(e->device);
+    HIPCHK(hipEventSynchronize(e->adj.ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, e->adj.ev[0], e->adj.ev[1]));
+    return OAMD_OK;
+}
+
+static int selfplay_move_enqueue(oamd_engine* e, const SelfplayParams& sp, int32_t* actions_dev, int32_t* finished_dev,
+                                 float* features_dev, float* policy_dev) {
+    launch_selfplay_move(e->view(), sp, 0, e->G, actions_dev, finished_dev, features_dev, policy_dev, e->stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+int oamd_engine_selfplay_move_adjudicated(oamd_engine* e, const oamd_selfplay_config* cfg, int32_t* actions_dev,
+                                          int32_t* finished_dev, float* features_dev, float* policy_dev,
+                                          int32_t max_empties, int32_t split, int32_t* margin_dev) {
+    if (int rc = adjudicate_checks(max_empties, finished_dev)) return rc;
+    if (int rc = selfplay_cfg_checks(cfg, features_dev, policy_dev)) return rc;
+    DeviceGuard dg(e->device);
+    SelfplayParams sp = selfplay_params(cfg);
+    if (max_empties == 0) return selfplay_move_enqueue(e, sp, actions_dev, finished_dev, features_dev, policy_dev);
+    if (int rc = adjudicate_begin(e, e->G, max_empties, split != 0, &sp)) return rc;
+    if (int rc = selfplay_move_enqueue(e, sp, actions_dev, finished_dev, features_dev, policy_dev)) return rc;
+    return adjudicate_resolve(e, e->G, max_empties, split != 0, finished_dev, margin_dev, false);
+}
+
+int oamd_engine_selfplay_move(oamd_engine* e, const oamd_selfplay_config* cfg, int32_t* actions_dev,
+                              int32_t* finished_dev, float* features_dev, float* policy_dev) {
+    return oamd_engine_selfplay_move_adjudicated(e, cfg, actions_dev, finished_dev, features_dev, policy_dev, 0, 0,
+                                                 nullptr);
 }
 
 // Free-running self-play: n_moves moves of every game, each game on its own
@@ -1660,7 +1799,7 @@ int oamd_engine_selfplay_move(oamd_engine* e, const oamd_selfplay_config* cfg, i
 // drains the queue), is 0. The
 // tail chunks' ResNet launches use the small looping grid (extra_grid): only
 // lagging games have rows then. Returns once the last chunk is enqueued.
-static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg, int n_moves,
+static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const SelfplayParams& sp, int n_moves,
                                int per_move, int32_t* actions, int32_t* finished, float* feat, float* pol) {
     if (int rc = e->ensure_remaining()) return rc;
     const GroupPlan P = plan_groups(e);
@@ -1669,7 +1808,6 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const oamd_selfpla
     const int steps = e->steps();
     const EngineView E = e->view();
     const NetView N = net->view();
-    const SelfplayParams sp = selfplay_params(cfg);
     const int budget = e->exact_interleaving && e->chain_budget > 0 ? e->chain_budget : 0;
     const int nlg = P.max_launches;
     if (int rc = fork_groups(e, P)) return rc;
@@ -1773,28 +1911,31 @@ int oamd_engine_set_free_running(oamd_engine* e, int32_t enable) {
     return OAMD_OK;
 }
 
-int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg, int32_t n_moves,
-                               int32_t per_move_outputs, int32_t* actions_dev, int32_t* finished_dev,
-                               float* features_dev, float* policy_dev) {
-    if (n_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "n_moves must be >= 0");
-    if (int rc = selfplay_cfg_checks(cfg, features_dev, policy_dev)) return rc;
-    if (int rc = native_search_checks(e, net)) return rc;
-    DeviceGuard dg(e->device);
+// the moves of oamd_engine_selfplay_steps on one of its three schedules; sp
+// carries the adjudication fields (pending slots laid out like `finished`)
+static int selfplay_steps_enqueue(oamd_engine* e, oamd_net* net, const SelfplayParams& sp, int32_t n_moves,
+                                  int32_t per_move_outputs, int32_t* actions_dev, int32_t* finished_dev,
+                                  float* features_dev, float* policy_dev) {
     const int G = e->G, C = 1 + 2 * e->cfg.history_size;
     // move i's outputs: the i-th slice of per-move buffers, or the same G-game buffers every move
     auto out = [&](int i, auto* p, int64_t per_game) { return p ? p + (per_move_outputs ? (int64_t)i * G * per_game : 0) : p; };
+    auto sp_of = [&](int i) {
+        SelfplayParams m = sp;
+        m.adj_pending = out(i, sp.adj_pending, 1);
+        return m;
+    };
     GroupPlan P = plan_groups(e);
     const bool split = e->thread_split();
     if (!split && e->free_running) {
         if (int rc = e->ensure_streams(P.K, P.K)) return rc;
-        return selfplay_steps_free(e, net, cfg, n_moves, per_move_outputs, actions_dev, finished_dev, features_dev,
+        return selfplay_steps_free(e, net, sp, n_moves, per_move_outputs, actions_dev, finished_dev, features_dev,
                                    policy_dev);
     }
     if (split || P.K == 1) {  // one stream: the plain sequence of calls
         for (int i = 0; i < n_moves; ++i) {
             if (int rc = oamd_engine_search(e, net, nullptr, nullptr)) return rc;
-            if (int rc = oamd_engine_selfplay_move(e, cfg, out(i, actions_dev, 1), out(i, finished_dev, 1),
-                                                   out(i, features_dev, 8 * C * 64), out(i, policy_dev, 8 * 65)))
+            if (int rc = selfplay_move_enqueue(e, sp_of(i), out(i, actions_dev, 1), out(i, finished_dev, 1),
+                                               out(i, features_dev, 8 * C * 64), out(i, policy_dev, 8 * 65)))
                 return rc;
         }
         return OAMD_OK;
@@ -1804,7 +1945,6 @@ int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfpla
     const int steps = e->steps();
     const EngineView E = e->view();
     const NetView N = net->view();
-    const SelfplayParams sp = selfplay_params(cfg);
     // Each group runs its own chain of searches and moves on its stream: its
     // move and the next search's first selection overlap the other groups'
     // last ResNet launches instead of waiting for a join after every move.
@@ -1817,7 +1957,7 @@ int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfpla
         if ((rc = timing_begin(e, steps + X, P.K, &timed))) break;
         if ((rc = enqueue_group_rounds(e, N, P, steps, X, timed, i > 0))) break;
         for (int k = 0; k < P.K; ++k)
-            launch_selfplay_move(E, sp, P.g0[k], P.ng[k], out(i, actions_dev, 1), out(i, finished_dev, 1),
+            launch_selfplay_move(E, sp_of(i), P.g0[k], P.ng[k], out(i, actions_dev, 1), out(i, finished_dev, 1),
                                  out(i, features_dev, 8 * C * 64), out(i, policy_dev, 8 * 65), P.st[k]);
         if (timed) timing_end_search(e, steps + X, P);
     }
@@ -1827,6 +1967,36 @@ int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfpla
     e->step_phase = 0;
     e->steps_left = 0;
     return OAMD_OK;
+}
+
+int oamd_engine_selfplay_steps_adjudicated(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg,
+                                           int32_t n_moves, int32_t per_move_outputs, int32_t* actions_dev,
+                                           int32_t* finished_dev, float* features_dev, float* policy_dev,
+                                           int32_t max_empties, int32_t split, int32_t* margin_dev) {
+    if (int rc = adjudicate_checks(max_empties, finished_dev)) return rc;
+    if (n_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "n_moves must be >= 0");
+    if (max_empties > 0 && n_moves > 1 && !per_move_outputs)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "adjudication needs per_move_outputs when n_moves > 1 (a move would overwrite the pending "
+                    "positions of the one before)");
+    if (int rc = selfplay_cfg_checks(cfg, features_dev, policy_dev)) return rc;
+    if (int rc = native_search_checks(e, net)) return rc;
+    DeviceGuard dg(e->device);
+    SelfplayParams sp = selfplay_params(cfg);
+    const int64_t n = max_empties > 0 ? (int64_t)n_moves * e->G : 0;
+    if (int rc = adjudicate_begin(e, n, max_empties, split != 0, &sp)) return rc;
+    if (int rc = selfplay_steps_enqueue(e, net, sp, n_moves, per_move_outputs, actions_dev, finished_dev,
+                                        features_dev, policy_dev))
+        return rc;
+    // after the groups have joined the caller's stream
+    return adjudicate_resolve(e, n, max_empties, split != 0, finished_dev, margin_dev, false);
+}
+
+int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg, int32_t n_moves,
+                               int32_t per_move_outputs, int32_t* actions_dev, int32_t* finished_dev,
+                               float* features_dev, float* policy_dev) {
+    return oamd_engine_selfplay_steps_adjudicated(e, net, cfg, n_moves, per_move_outputs, actions_dev, finished_dev,
+                                                  features_dev, policy_dev, 0, 0, nullptr);
 }
 
 int oamd_engine_random_openings(oamd_engine* e, int32_t max_moves, uint64_t seed) {
@@ -1885,20 +2055,35 @@ int oamd_arena_begin(oamd_engine* a, oamd_engine* b, const int32_t* openings_dev
     return OAMD_OK;
 }
 
-int oamd_arena_move(oamd_engine* a, oamd_engine* b, const oamd_selfplay_config* cfg, int32_t* actions_dev,
-                    int32_t* finished_dev, int32_t* discs_dev, int32_t* remaining_dev) {
+// The pending slots of a match (engine A's workspace, one per match) outlive a
+// ply: arena_play zeroes them once and resolves once after the last ply; a
+// single arena_move zeroes, moves and resolves.
+int oamd_arena_move_adjudicated(oamd_engine* a, oamd_engine* b, const oamd_selfplay_config* cfg,
+                                int32_t* actions_dev, int32_t* finished_dev, int32_t* discs_dev,
+                                int32_t* remaining_dev, int32_t max_empties, int32_t split, int32_t* margin_dev) {
+    if (int rc = adjudicate_checks(max_empties, finished_dev)) return rc;
     if (int rc = arena_checks(a, b)) return rc;
     if (int rc = arena_cfg_checks(cfg)) return rc;
     DeviceGuard dg(a->device);
     SelfplayParams sp{cfg->temperature_moves, cfg->temperature, 0, 0};
+    if (max_empties > 0)
+        if (int rc = adjudicate_begin(a, a->G, max_empties, split != 0, &sp)) return rc;
     launch_arena_move(a->view(), b->view(), sp, actions_dev, finished_dev, discs_dev, remaining_dev, a->stream);
     LAUNCHCHK();
+    if (max_empties > 0) return adjudicate_resolve(a, a->G, max_empties, split != 0, finished_dev, margin_dev, true);
     return OAMD_OK;
 }
 
-int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* net_b, const oamd_selfplay_config* cfg,
-                    int32_t max_plies, int32_t* actions_dev, int32_t* finished_dev, int32_t* discs_dev,
-                    int32_t* plies_host) {
+int oamd_arena_move(oamd_engine* a, oamd_engine* b, const oamd_selfplay_config* cfg, int32_t* actions_dev,
+                    int32_t* finished_dev, int32_t* discs_dev, int32_t* remaining_dev) {
+    return oamd_arena_move_adjudicated(a, b, cfg, actions_dev, finished_dev, discs_dev, remaining_dev, 0, 0, nullptr);
+}
+
+int oamd_arena_play_adjudicated(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* net_b,
+                                const oamd_selfplay_config* cfg, int32_t max_plies, int32_t* actions_dev,
+                                int32_t* finished_dev, int32_t* discs_dev, int32_t* plies_host, int32_t max_empties,
+                                int32_t split, int32_t* margin_dev) {
+    if (int rc = adjudicate_checks(max_empties, finished_dev)) return rc;
     if (int rc = arena_checks(a, b)) return rc;
     if (int rc = arena_cfg_checks(cfg)) return rc;
     if (int rc = native_search_checks(a, net_a)) return rc;
@@ -1911,6 +2096,9 @@ int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* n
     const int G = a->G;
     hipStream_t s = a->stream;
     int32_t* remaining = a->remaining.dev;
+    SelfplayParams sp{cfg->temperature_moves, cfg->temperature, 0, 0};
+    if (max_empties > 0)
+        if (int rc = adjudicate_begin(a, G, max_empties, split != 0, &sp)) return rc;
     // every byte 0xFF: action -1 in the plies that are never enqueued
     if (max_plies > 0) HIPCHK(hipMemsetAsync(actions_dev, 0xFF, sizeof(int32_t) * (size_t)max_plies * G, s));
     HIPCHK(hipMemsetAsync(finished_dev, 0, sizeof(int32_t) * G, s));
@@ -1928,12 +2116,23 @@ int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* n
             // only the side to move of each match is active in its engine
             if (int rc = oamd_engine_search(a, net_a, nullptr, nullptr)) return rc;
             if (int rc = oamd_engine_search(b, net_b, nullptr, nullptr)) return rc;
-            if (int rc = oamd_arena_move(a, b, cfg, actions_dev + (size_t)ply * G, finished_dev, discs_dev, remaining))
-                return rc;
+            launch_arena_move(a->view(), b->view(), sp, actions_dev + (size_t)ply * G, finished_dev, discs_dev,
+                              remaining, s);
+            LAUNCHCHK();
         }
     }
     if (plies_host) *plies_host = ply;
+    // the slots collected every match that ended in this call: margin is
+    // written for all G (INT32_MIN: the match did not end here)
+    if (max_empties > 0) return adjudicate_resolve(a, G, max_empties, split != 0, finished_dev, margin_dev, false);
     return OAMD_OK;
+}
+
+int oamd_arena_play(oamd_engine* a, oamd_net* net_a, oamd_engine* b, oamd_net* net_b, const oamd_selfplay_config* cfg,
+                    int32_t max_plies, int32_t* actions_dev, int32_t* finished_dev, int32_t* discs_dev,
+                    int32_t* plies_host) {
+    return oamd_arena_play_adjudicated(a, net_a, b, net_b, cfg, max_plies, actions_dev, finished_dev, discs_dev,
+                                       plies_host, 0, 0, nullptr);
 }
 
 // ---------------------------------------------------------------------------

@@ -57,6 +57,11 @@ static_assert(sizeof(GameState) == 128, "GameState layout");
 // Arena status bits reported in `finished` beside the outcome (bits 0-1) and
 // the self-play driver's bits 2-3 (tree.hip k_arena_move)
 constexpr int32_t kArenaDesync = 16;
+// ... and of every adjudicating driver: the game was ended at
+// this move by the exact solver (in GameState::arena: the match is over); the
+// solver flagged the position (cannot happen for an engine position)
+constexpr int32_t kFinAdjudicated = 32;
+constexpr int32_t kFinSolverFlag = 64;
 
 // Packed NN input row (FW uint64 words): word 0 = meta, then (p1, p2) of the
 // leaf and its H-1 nearest ancestors, untransformed. meta bit 0 = player - 1,

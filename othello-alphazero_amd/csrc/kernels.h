@@ -15,6 +15,14 @@ struct SelfplayParams {
     float temperature;
     int32_t opening_moves;
     int32_t emit_targets;
+    // adjudication: 0 = off; else a searched move that leaves a
+    // non-terminal root with at most this many empties ends the game there, and
+    // the root goes to the pending slot of this launch's `finished` word
+    // (adjudicate.hip fills in the outcome). adj_pending also receives the final
+    // position of a game that ended on the board (player 0).
+    int32_t adj_empties = 0;
+    int32_t adj_pad = 0;
+    oamd_position* adj_pending = nullptr;
 };
 
 // tree.hip
@@ -64,6 +72,14 @@ void launch_tree_free(const EngineView& E, hipStream_t s, int g0, int ng, int B,
                       int budget, bool timed, const SelfplayParams& sp, int n_moves, int per_move, int32_t* actions,
                       int32_t* finished, float* feat, float* pol, int32_t* remaining);
 void launch_status(const EngineView& E, int32_t* out, hipStream_t s);
+
+// adjudicate.hip: after the solver ran over the n pending positions (score,
+// flags), write the outcome bits, kFinAdjudicated / kFinSolverFlag and the
+// margin of every slot. accumulate = 0 (self-play): margin[i] is written for
+// every slot, INT32_MIN where no game ended. accumulate = 1 (arena): only the
+// slots of matches that ended are touched.
+void launch_adjudicate_apply(const oamd_position* pending, const int32_t* score, const int32_t* flags, int64_t n,
+                             int32_t* finished, int32_t* margin, int accumulate, hipStream_t s);
 void launch_legal_moves(const uint64_t* me, const uint64_t* opp, uint64_t* out, int64_t n,
                         hipStream_t s);
 void launch_flips(const uint64_t* mv, const uint64_t* me, const uint64_t* opp, uint64_t* out,

@@ -661,6 +661,34 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                                                   reinterpret_cast<int32_t*>(finished), reinterpret_cast<float*>(feat),
                                                   reinterpret_cast<float*>(pol)));
              })
+        // adjudication by the exact solver (max_empties 0 = the calls above); margin may be 0
+        .def("selfplay_move_adjudicated",
+             [](Engine& e, int temperature_moves, float temperature, int opening_moves, bool emit, uintptr_t actions,
+                uintptr_t finished, uintptr_t feat, uintptr_t pol, int max_empties, bool split, uintptr_t margin) {
+                 oamd_selfplay_config c{temperature_moves, temperature, opening_moves, emit ? 1 : 0};
+                 check(oamd_engine_selfplay_move_adjudicated(
+                     e.h, &c, reinterpret_cast<int32_t*>(actions), reinterpret_cast<int32_t*>(finished),
+                     reinterpret_cast<float*>(feat), reinterpret_cast<float*>(pol), max_empties, split ? 1 : 0,
+                     reinterpret_cast<int32_t*>(margin)));
+             })
+        .def("selfplay_steps_adjudicated",
+             [](Engine& e, uintptr_t net, int n_moves, int temperature_moves, float temperature, int opening_moves,
+                bool emit, bool per_move_outputs, uintptr_t actions, uintptr_t finished, uintptr_t feat, uintptr_t pol,
+                int max_empties, bool split, uintptr_t margin) {
+                 oamd_selfplay_config c{temperature_moves, temperature, opening_moves, emit ? 1 : 0};
+                 check(oamd_engine_selfplay_steps_adjudicated(
+                     e.h, reinterpret_cast<oamd_net*>(net), &c, n_moves, per_move_outputs ? 1 : 0,
+                     reinterpret_cast<int32_t*>(actions), reinterpret_cast<int32_t*>(finished),
+                     reinterpret_cast<float*>(feat), reinterpret_cast<float*>(pol), max_empties, split ? 1 : 0,
+                     reinterpret_cast<int32_t*>(margin)));
+             })
+        .def("adjudicate_ms",
+             [](Engine& e) {
+                 float ms = 0.0f;
+                 int64_t n = 0;
+                 check(oamd_engine_adjudicate_ms(e.h, &ms, &n));
+                 return py::make_tuple(ms, n);
+             })
         .def("random_openings",
              [](Engine& e, int max_moves, uint64_t seed) { check(oamd_engine_random_openings(e.h, max_moves, seed)); })
         .def("game_key",
@@ -695,6 +723,29 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                  check(oamd_arena_play(a.h, reinterpret_cast<oamd_net*>(net_a), b.h, reinterpret_cast<oamd_net*>(net_b),
                                        &c, max_plies, reinterpret_cast<int32_t*>(actions),
                                        reinterpret_cast<int32_t*>(finished), reinterpret_cast<int32_t*>(discs), &plies));
+                 return plies;
+             })
+        .def("arena_move_adjudicated",
+             [](Engine& a, Engine& b, int temperature_moves, float temperature, uintptr_t actions, uintptr_t finished,
+                uintptr_t discs, uintptr_t remaining, int max_empties, bool split, uintptr_t margin) {
+                 oamd_selfplay_config c{temperature_moves, temperature, 0, 0};
+                 check(oamd_arena_move_adjudicated(a.h, b.h, &c, reinterpret_cast<int32_t*>(actions),
+                                                   reinterpret_cast<int32_t*>(finished),
+                                                   reinterpret_cast<int32_t*>(discs),
+                                                   reinterpret_cast<int32_t*>(remaining), max_empties, split ? 1 : 0,
+                                                   reinterpret_cast<int32_t*>(margin)));
+             })
+        .def("arena_play_adjudicated",
+             [](Engine& a, uintptr_t net_a, Engine& b, uintptr_t net_b, int temperature_moves, float temperature,
+                int max_plies, uintptr_t actions, uintptr_t finished, uintptr_t discs, int max_empties, bool split,
+                uintptr_t margin) {
+                 oamd_selfplay_config c{temperature_moves, temperature, 0, 0};
+                 int32_t plies = 0;
+                 check(oamd_arena_play_adjudicated(
+                     a.h, reinterpret_cast<oamd_net*>(net_a), b.h, reinterpret_cast<oamd_net*>(net_b), &c, max_plies,
+                     reinterpret_cast<int32_t*>(actions), reinterpret_cast<int32_t*>(finished),
+                     reinterpret_cast<int32_t*>(discs), &plies, max_empties, split ? 1 : 0,
+                     reinterpret_cast<int32_t*>(margin)));
                  return plies;
              })
         .def("enable_timing", [](Engine& e, int every) { check(oamd_engine_enable_timing(e.h, every)); },

@@ -40,7 +40,7 @@ constexpr int kCommitWaves = kCommitThreads / 64;
 constexpr int kGatherWaves = 4;
 
 // finished word of the self-play driver (tree.hip selfplay_move_game)
-constexpr int kFinOutcome = 3, kFinNoTargets = 4, kFinOverflow = 8;
+constexpr int kFinOutcome = 3, kFinNoTargets = 4, kFinOverflow = 8, kFinSolverFlag = 64;
 
 __device__ __forceinline__ void raise_flag(int64_t* counters, int bit) {
     // sticky OR: the result does not depend on the order of the updates
@@ -64,6 +64,8 @@ __global__ __launch_bounds__(64) void k_replay_add(oamd_replay_view V, const int
     if (fin & kFinOverflow) err |= OAMD_REPLAY_OVERFLOW;
     if (played && (fin & kFinNoTargets)) err |= OAMD_REPLAY_NO_TARGETS;
     if (played && m >= V.max_moves) err |= OAMD_REPLAY_TOO_LONG;
+    // an adjudicated game the solver gave no outcome for: the game is over, its moves have no value target
+    if (fin & kFinSolverFlag) err |= OAMD_REPLAY_SOLVER_FLAG;
     if (played && !err) {
         const float* f = feat + (size_t)g * 8 * C * 64;  // transform 0: inverse_transform(sq, 0) == sq
         uint64_t mine = 0;
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(64) void k_replay_add(oamd_replay_view V, const int
     }
     if (lane == 0) {
         if (err) raise_flag(V.counters, err);
-        const bool done = (fin & kFinOutcome) != 0;
+        const bool done = (fin & (kFinOutcome | kFinSolverFlag)) != 0;
         V.pending[g] = done && !err ? m : -1;
         V.moves[g] = done && err ? 0 : m;
     }

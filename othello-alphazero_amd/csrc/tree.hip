@@ -1272,11 +1272,22 @@ __device__ __forceinline__ int choose_root_action(const EngineView& E, const Gam
     return action_of_child(rp.legal, j);
 }
 
+// The pending slot of an adjudicating driver (SelfplayParams::adj_pending):
+// the root as an oamd_position, player 0 for a game that ended on the board.
+__device__ __forceinline__ void store_pending(oamd_position* slot, int player, const NodePos& p) {
+    slot->player = player;
+    slot->reserved = 0;
+    slot->player1_discs = p.p1;
+    slot->player2_discs = p.p2;
+    slot->legal_moves = p.legal;
+    slot->next_legal_moves = p.next_legal;
+}
+
 // One self-play move of game g (one wave): outputs at index g of the given
 // per-move slices.
 __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const SelfplayParams& sp, int g,
                                                    int32_t* actions, int32_t* finished, float* feat_out,
-                                                   float* pol_out) {
+                                                   float* pol_out, oamd_position* pending) {
     const int lane = lane_id();
     GameState* gs = E.games + g;
     const size_t base = (size_t)g * E.cap;
@@ -1309,10 +1320,23 @@ __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const Se
     if (lane == 0) {
         const int r2 = gs->root;
         const NodeLink l2 = load_link(E.link + base + r2);
-        if (l2.player == 0) {
+        bool over = l2.player == 0;
+        if (over) {
             const NodePos p2 = E.pos[base + r2];
             const int b = popcount64(p2.p1), w = popcount64(p2.p2);
             fin = b > w ? 2 : (b < w ? 3 : 1);  // 1 draw, 2 black won, 3 white won
+            if (pending) store_pending(pending + g, 0, p2);
+        } else if (sp.adj_empties > 0 && action >= 0) {
+            // adjudication: the searched move left a root the solver finishes
+            // exactly; the outcome bits come from adjudicate.hip
+            const NodePos p2 = E.pos[base + r2];
+            if (64 - popcount64(p2.p1 | p2.p2) <= sp.adj_empties) {
+                fin = kFinAdjudicated;
+                over = true;
+                if (pending) store_pending(pending + g, l2.player, p2);
+            }
+        }
+        if (over) {
             const uint64_t key = gs->key;
             const uint64_t ev = gs->event;
             init_game(E, g, key ^ mix64(ev + 0xA5A5A5A5ULL));
@@ -1336,7 +1360,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(EngineView E, SelfplayPara
         }
         return;
     }
-    selfplay_move_game(E, sp, g, actions, finished, feat_out, pol_out);
+    selfplay_move_game(E, sp, g, actions, finished, feat_out, pol_out, sp.adj_pending);
 }
 
 // Per-game search mask (oamd_engine_set_active): k_tree, k_selfplay_move and
@@ -1401,7 +1425,7 @@ __global__ void k_arena_count(EngineView EA, int32_t* remaining) {
     if (g >= EA.G) return;
     const GameState* ga = EA.games + g;
     if (ga->arena != 0 && load_link(EA.link + (size_t)g * EA.cap + ga->root).player != 0 &&
-        (ga->arena & kArenaDesync) == 0)
+        (ga->arena & (kArenaDesync | kFinAdjudicated)) == 0)
         atomicAdd(remaining, 1);
 }
 
@@ -1409,7 +1433,9 @@ __global__ void k_arena_count(EngineView EA, int32_t* remaining) {
 // 0-1 the outcome once the match ends (1 draw, 2 black won, 3 white won, as
 // k_selfplay_move reports it), bit 2 a move from an unexpanded root (uniform),
 // bit 3 a node pool overflowed, bit 4 the two trees' roots differ (the match
-// stops). actions[g] = the action played, -1 when the match is over.
+// stops), bit 5 the match was adjudicated at this ply (sp.adj_empties > 0: the
+// outcome bits follow from adjudicate.hip). actions[g] = the action played, -1
+// when the match is over.
 __global__ __launch_bounds__(64) void k_arena_move(EngineView EA, EngineView EB, SelfplayParams sp, int32_t* actions,
                                                    int32_t* finished, int32_t* discs, int32_t* remaining) {
     const int g = (int)blockIdx.x;
@@ -1423,7 +1449,7 @@ __global__ __launch_bounds__(64) void k_arena_move(EngineView EA, EngineView EB,
     const NodePos pa = EA.pos[base_a + ga->root];
     const NodePos pb = EB.pos[base_b + gb->root];
     int action = -1;
-    if ((arena & 3) == 0 || (arena & kArenaDesync) || la.player == 0) {
+    if ((arena & 3) == 0 || (arena & (kArenaDesync | kFinAdjudicated)) || la.player == 0) {
         if (lane == 0 && actions) actions[g] = -1;
         return;
     }
@@ -1465,8 +1491,22 @@ __global__ __launch_bounds__(64) void k_arena_move(EngineView EA, EngineView EB,
                 discs[2 * g + 1] = w;
             }
             if (remaining) atomicSub(remaining, 1);
+            if (sp.adj_pending) store_pending(sp.adj_pending + g, 0, p2);
+        } else if (sp.adj_empties > 0) {
+            // adjudication: the match stops here, adjudicate.hip reports the exact result
+            const NodePos p2 = EA.pos[base_a + r2];
+            if (64 - popcount64(p2.p1 | p2.p2) <= sp.adj_empties) {
+                fin = kFinAdjudicated;
+                ga->arena = gb->arena = arena | kFinAdjudicated;
+                if (discs) {
+                    discs[2 * g] = popcount64(p2.p1);
+                    discs[2 * g + 1] = popcount64(p2.p2);
+                }
+                if (remaining) atomicSub(remaining, 1);
+                if (sp.adj_pending) store_pending(sp.adj_pending + g, l2.player, p2);
+            }
         }
-        arena_set_mover(ga, gb, l2.player);
+        arena_set_mover(ga, gb, fin & kFinAdjudicated ? 0 : l2.player);
         if (actions) actions[g] = action;
         if (finished && (fin | status)) finished[g] |= fin | status;
     }
@@ -1546,7 +1586,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_tre
         const size_t slot = per_move ? (size_t)(n_moves - moves) * E.G : 0;
         const size_t C = 1 + 2 * (size_t)E.H;
         selfplay_move_game(E, sp, g, actions ? actions + slot : nullptr, finished ? finished + slot : nullptr,
-                           feat_out ? feat_out + slot * 8 * C * 64 : nullptr, pol_out ? pol_out + slot * 8 * 65 : nullptr);
+                           feat_out ? feat_out + slot * 8 * C * 64 : nullptr, pol_out ? pol_out + slot * 8 * 65 : nullptr,
+                           sp.adj_pending ? sp.adj_pending + slot : nullptr);
         --moves;
         __builtin_amdgcn_wave_barrier();
         wait_stores();  // (a compiler barrier too: the reloads below see the move's stores)

@@ -16,7 +16,9 @@ board symmetries when a minibatch is gathered. ``solve_endgames`` /
 ``solve_position`` / ``endgame_move_loss`` solve the last plies exactly (GPU
 and host) and measure a move against perfect play;
 ``ReplayBuffer(track_exact=True).relabel_endgames`` uses the same solver to
-give the buffer's last plies exact value targets.
+give the buffer's last plies exact value targets, and ``adjudicate_empties=K``
+(self-play, arena; ``adjudicate`` is the rule on the host) ends running games
+at K empties with the exact result.
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -41,6 +43,7 @@ from .native import NativeNet, load_checkpoint  # noqa: E402,F401
 from .selfplay import SelfPlayCollector, self_play  # noqa: E402,F401
 from .replay import ReplayBuffer  # noqa: E402,F401
 from .endgame import EndgameSolution, endgame_move_loss, solve_endgames, solve_position  # noqa: E402,F401
+from .adjudication import adjudicate  # noqa: E402,F401
 from .training import (  # noqa: E402,F401
     SampleBuffer,
     alphazero_loss,
@@ -73,4 +76,5 @@ __all__ = [
     "solve_endgames",
     "solve_position",
     "endgame_move_loss",
+    "adjudicate",
 ]

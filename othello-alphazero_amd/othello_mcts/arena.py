@@ -23,6 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from .adjudication import MARGIN_NONE, check_adjudicate_empties
 from .batched import BatchedMCTS
 from .native import resolve
 from .synthetic import _splitmix_stream
@@ -34,6 +35,8 @@ _OUTCOME = 3
 _UNEXPANDED = 4
 _OVERFLOW = 8
 _DESYNC = 16
+_ADJUDICATED = 32  # the match was ended by the exact solver (othello_mcts.adjudication)
+_SOLVER_FLAG = 64
 
 
 def paired_openings(num_games: int, plies: int, seed: int = 0, position_cls=None) -> np.ndarray:
@@ -64,13 +67,25 @@ class ArenaResult:
     actions (plies, G): the action of every ply after the opening, -1 once a
     match is over; result (G): play_game's return, 0 draw, 1 black won, 2 white
     won (UNFINISHED = -1: still running when play stopped); a_is_white (G) bool;
-    discs (G, 2): black and white discs at the end; plies: plies played."""
+    discs (G, 2): black and white discs at the end (of an adjudicated match: at
+    the adjudicated position); plies: plies played; margin (G): the final score
+    seen from black, black minus white discs for a match that ended on the
+    board, the exact result of the adjudicated position otherwise (0 for an
+    unfinished match); adjudicated (G) bool."""
 
     actions: torch.Tensor
     result: torch.Tensor
     a_is_white: torch.Tensor
     discs: torch.Tensor
     plies: int
+    margin: torch.Tensor = None
+    adjudicated: torch.Tensor = None
+
+    def __post_init__(self) -> None:
+        if self.adjudicated is None:
+            self.adjudicated = torch.zeros(self.result.shape, dtype=torch.bool)
+        if self.margin is None:
+            self.margin = torch.where(self.result >= 0, self.discs[:, 0] - self.discs[:, 1], 0).to(torch.int64)
 
     def wdl(self) -> tuple[int, int, int]:
         """(wins, draws, losses) of net A."""
@@ -96,6 +111,10 @@ class ArenaResult:
                 continue
             out.append({"player1": id_b if w else id_a, "player2": id_a if w else id_b, "result": int(r)})
         return out
+
+    def margin_a(self) -> torch.Tensor:
+        """(G) the margin seen from net A (0 for an unfinished match)."""
+        return torch.where(self.a_is_white, -self.margin, self.margin)
 
 
 def _result_from_status(status: torch.Tensor) -> torch.Tensor:
@@ -123,6 +142,7 @@ class Arena:
         self._status = torch.zeros(G, dtype=torch.int32, device=self.device)
         self._discs = torch.zeros((G, 2), dtype=torch.int32, device=self.device)
         self._remaining = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._margin = torch.full((G,), MARGIN_NONE, dtype=torch.int32, device=self.device)
         self.a_is_white = torch.zeros(G, dtype=torch.bool)
         self.opening_plies = 0
         self.seed = 0
@@ -175,6 +195,7 @@ class Arena:
         self._status.zero_()
         self._discs.zero_()
         self._remaining.zero_()
+        self._margin.fill_(MARGIN_NONE)
         self.a_is_white = torch.from_numpy(white.copy())
         self.opening_plies = op.shape[1]
         self._begun = True
@@ -188,28 +209,43 @@ class Arena:
         rb = self.b.search(net_b, sync=sync)
         return (ra, rb) if sync else None
 
-    def move(self, temperature_moves: int = 0, temperature: float = 1.0) -> dict[str, torch.Tensor]:
+    def move(self, temperature_moves: int = 0, temperature: float = 1.0, adjudicate_empties: int = 0,
+             split: bool = False) -> dict[str, torch.Tensor]:
         """One ply of every match from the searched roots (device tensors,
         overwritten by the next call): actions (G), -1 once a match is over;
-        finished (G): the cumulative status word of oamd_arena_move; discs (G, 2)."""
+        finished (G): the cumulative status word of oamd_arena_move; discs (G, 2).
+        adjudicate_empties = K > 0: a ply that leaves a non-terminal position
+        with at most K empties ends the match with its exact result (bit 5 of
+        finished; othello_mcts.adjudication), and ``margin`` (G, cumulative) is
+        the final score seen from black of every match that has ended since
+        reset(), MARGIN_NONE for the others."""
+        k = check_adjudicate_empties(adjudicate_empties)
         if not self._begun:
             raise RuntimeError("Arena.move before Arena.reset")
         self._streams()
-        self.a.engine.arena_move(self.b.engine, temperature_moves, temperature, self._actions.data_ptr(),
-                                 self._status.data_ptr(), self._discs.data_ptr(), 0)
-        return {"actions": self._actions, "finished": self._status, "discs": self._discs}
+        if k == 0:
+            self.a.engine.arena_move(self.b.engine, temperature_moves, temperature, self._actions.data_ptr(),
+                                     self._status.data_ptr(), self._discs.data_ptr(), 0)
+            return {"actions": self._actions, "finished": self._status, "discs": self._discs}
+        self.a.engine.arena_move_adjudicated(self.b.engine, temperature_moves, temperature, self._actions.data_ptr(),
+                                             self._status.data_ptr(), self._discs.data_ptr(), 0, k, bool(split),
+                                             self._margin.data_ptr())
+        return {"actions": self._actions, "finished": self._status, "discs": self._discs, "margin": self._margin}
 
     def _native(self, net, mcts):
         return resolve(net, self.device.index, mcts.config.history_size)
 
     def play(self, net_a, net_b, max_plies: int = 128, temperature_moves: int = 0,
-             temperature: float = 1.0) -> ArenaResult:
+             temperature: float = 1.0, adjudicate_empties: int = 0, split: bool = False) -> ArenaResult:
         """Play the matches begun by reset() (called here if it was not) to the
         end, at most ``max_plies`` plies: one fused call when both nets are
         native, the search / move loop otherwise. Matches still running after
         max_plies have result UNFINISHED. Raises RuntimeError when a node pool
         overflowed, a descent hit the depth cap or the two trees of a match
-        disagree, naming the matches."""
+        disagree, naming the matches. adjudicate_empties / split: as move();
+        the result's ``adjudicated`` and ``margin`` say which matches the solver
+        ended and by how much."""
+        k = check_adjudicate_empties(adjudicate_empties)
         if not self._begun:
             self.reset()
         G = self.num_games
@@ -217,17 +253,23 @@ class Arena:
         if na is not None and nb is not None:
             self._streams()
             actions = torch.empty((max(0, max_plies), G), dtype=torch.int32, device=self.device)
-            plies = self.a.engine.arena_play(na.handle, self.b.engine, nb.handle, temperature_moves, temperature,
-                                             max_plies, actions.data_ptr(), self._status.data_ptr(),
-                                             self._discs.data_ptr())
+            if k > 0:
+                plies = self.a.engine.arena_play_adjudicated(na.handle, self.b.engine, nb.handle, temperature_moves,
+                                                             temperature, max_plies, actions.data_ptr(),
+                                                             self._status.data_ptr(), self._discs.data_ptr(), k,
+                                                             bool(split), self._margin.data_ptr())
+            else:
+                plies = self.a.engine.arena_play(na.handle, self.b.engine, nb.handle, temperature_moves, temperature,
+                                                 max_plies, actions.data_ptr(), self._status.data_ptr(),
+                                                 self._discs.data_ptr())
             actions = actions[:plies]
             status = self._status.cpu()
         else:
             rows = []
             status = self._status.cpu()
-            while len(rows) < max_plies and bool(((status & (_OUTCOME | _DESYNC)) == 0).any()):
+            while len(rows) < max_plies and bool(((status & (_OUTCOME | _DESYNC | _SOLVER_FLAG)) == 0).any()):
                 self.search(net_a, net_b)
-                out = self.move(temperature_moves, temperature)
+                out = self.move(temperature_moves, temperature, k, split)
                 rows.append(out["actions"].clone())
                 status = out["finished"].cpu()
             actions = torch.stack(rows) if rows else torch.empty((0, G), dtype=torch.int32, device=self.device)
@@ -239,13 +281,22 @@ class Arena:
         acts = acts[:n]
         self._raise_on_trouble(status)
         self._begun = False
-        return ArenaResult(actions=acts, result=_result_from_status(status), a_is_white=self.a_is_white.clone(),
-                           discs=self._discs.cpu().to(torch.int64), plies=n)
+        result = _result_from_status(status)
+        discs = self._discs.cpu().to(torch.int64)
+        adjudicated = (status & _ADJUDICATED) != 0
+        margin = torch.where(result >= 0, discs[:, 0] - discs[:, 1], 0)
+        if k > 0:
+            margin = torch.where(adjudicated, self._margin.cpu().to(torch.int64), margin)
+        return ArenaResult(actions=acts, result=result, a_is_white=self.a_is_white.clone(), discs=discs, plies=n,
+                           margin=margin, adjudicated=adjudicated)
 
     def _raise_on_trouble(self, status: torch.Tensor) -> None:
         def games(bit):
             return torch.nonzero(status & bit).flatten().tolist()
 
+        if games(_SOLVER_FLAG):
+            raise RuntimeError(f"arena: the exact solver flagged the adjudicated position of match(es) "
+                               f"{games(_SOLVER_FLAG)}")
         if games(_DESYNC):
             raise RuntimeError(f"arena: the two trees of match(es) {games(_DESYNC)} hold different positions")
         if games(_OVERFLOW):

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from ._othello_mcts_impl import SearchConfig, _Engine
+from .adjudication import check_adjudicate_empties
 from .native import NativeNet, resolve
 
 
@@ -61,6 +62,7 @@ class BatchedMCTS:
         C = 1 + 2 * history_size
         self._targets_f = None
         self._targets_p = None
+        self._margin = None
         self._C = C
 
     @property
@@ -179,10 +181,19 @@ class BatchedMCTS:
         self.engine.apply_actions(a.data_ptr())
 
     def selfplay_move(self, temperature_moves: int = 12, temperature: float = 1.0, opening_moves: int = 0,
-                      emit_targets: bool = False) -> dict[str, torch.Tensor]:
+                      emit_targets: bool = False, adjudicate_empties: int = 0,
+                      split: bool = False) -> dict[str, torch.Tensor]:
         """One self-play move for every game (train.py:404-452 on device): choose the
         move from the root visits, (optionally) emit the 8-fold targets, apply it, and
-        restart finished games from a random opening. Returns device tensors."""
+        restart finished games from a random opening. Returns device tensors.
+
+        adjudicate_empties = K > 0 (othello_mcts.adjudication): a move that leaves
+        a non-terminal root with at most K empties ends the game there with the
+        exact result (``split``: by the split solver); ``finished`` carries
+        FIN_ADJUDICATED and the outcome, and ``out["margin"]`` (G) the exact
+        margin seen from black (disc difference for a game that ended on the
+        board, MARGIN_NONE where no game ended)."""
+        k = check_adjudicate_empties(adjudicate_empties)
         self._stream()
         if emit_targets and self._targets_f is None:
             self._targets_f = torch.empty((self.num_games, 8, self._C, 8, 8), dtype=torch.float32,
@@ -190,9 +201,18 @@ class BatchedMCTS:
             self._targets_p = torch.empty((self.num_games, 8, 65), dtype=torch.float32, device=self.device)
         f = self._targets_f.data_ptr() if emit_targets else 0
         p = self._targets_p.data_ptr() if emit_targets else 0
-        self.engine.selfplay_move(temperature_moves, temperature, opening_moves, emit_targets,
-                                  self._actions.data_ptr(), self._finished.data_ptr(), f, p)
+        if k > 0:
+            if self._margin is None:
+                self._margin = torch.empty(self.num_games, dtype=torch.int32, device=self.device)
+            self.engine.selfplay_move_adjudicated(temperature_moves, temperature, opening_moves, emit_targets,
+                                                  self._actions.data_ptr(), self._finished.data_ptr(), f, p, k,
+                                                  bool(split), self._margin.data_ptr())
+        else:
+            self.engine.selfplay_move(temperature_moves, temperature, opening_moves, emit_targets,
+                                      self._actions.data_ptr(), self._finished.data_ptr(), f, p)
         out = {"actions": self._actions, "finished": self._finished}
+        if k > 0:
+            out["margin"] = self._margin
         if emit_targets:
             out["features"] = self._targets_f
             out["policy"] = self._targets_p
@@ -200,13 +220,17 @@ class BatchedMCTS:
 
     def selfplay_steps(self, neural_net, n_moves: int, temperature_moves: int = 12, temperature: float = 1.0,
                        opening_moves: int = 0, emit_targets: bool = False,
-                       keep_all: bool = True) -> dict[str, torch.Tensor]:
+                       keep_all: bool = True, adjudicate_empties: int = 0,
+                       split: bool = False) -> dict[str, torch.Tensor]:
         """n_moves x (search(net) + selfplay_move(...)) in one enqueue, same results
         move for move; each pipeline group chains its searches and moves on its own
         stream, so the per-move join disappears (oamd_engine_selfplay_steps).
         keep_all: outputs shaped (n_moves, G, ...); else only the last move's
         (G, ...), every move writing the same buffers. Native net (or a module
-        search() would convert) only."""
+        search() would convert) only. adjudicate_empties / split: as
+        selfplay_move, ``out["margin"]`` shaped like ``finished``; with more than
+        one move it needs keep_all=True (ValueError otherwise)."""
+        k = check_adjudicate_empties(adjudicate_empties, max(0, int(n_moves)), keep_all)
         self._stream()
         net = resolve(neural_net, self.device.index, self.config.history_size)
         if net is None:
@@ -219,11 +243,18 @@ class BatchedMCTS:
         if emit_targets:
             feat = torch.empty(lead + (self.num_games, 8, self._C, 8, 8), dtype=torch.float32, device=self.device)
             pol = torch.empty(lead + (self.num_games, 8, 65), dtype=torch.float32, device=self.device)
-        self.engine.selfplay_steps(net.handle, n, temperature_moves, temperature, opening_moves, emit_targets,
-                                   keep_all, actions.data_ptr(), finished.data_ptr(),
-                                   feat.data_ptr() if feat is not None else 0,
-                                   pol.data_ptr() if pol is not None else 0)
+        fp = feat.data_ptr() if feat is not None else 0
+        pp = pol.data_ptr() if pol is not None else 0
         out = {"actions": actions, "finished": finished}
+        if k > 0:
+            margin = torch.empty_like(actions)
+            self.engine.selfplay_steps_adjudicated(net.handle, n, temperature_moves, temperature, opening_moves,
+                                                   emit_targets, keep_all, actions.data_ptr(), finished.data_ptr(),
+                                                   fp, pp, k, bool(split), margin.data_ptr())
+            out["margin"] = margin
+        else:
+            self.engine.selfplay_steps(net.handle, n, temperature_moves, temperature, opening_moves, emit_targets,
+                                       keep_all, actions.data_ptr(), finished.data_ptr(), fp, pp)
         if emit_targets:
             out["features"] = feat
             out["policy"] = pol

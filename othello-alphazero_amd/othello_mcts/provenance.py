@@ -19,7 +19,7 @@ INCLUDE = Path(__file__).resolve().parent.parent.parent / "include"
 FAMILIES = {
     "resnet": ["resnet.hip", "kernels.h"],
     "tree": ["tree.hip", "engine.h", "bitboard.h", "rng.h", "kernels.h"],
-    "all": ["bitboard.h", "capi.hip", "engine.h", "kernels.h", "replay.h", "replay.hip", "resnet.hip", "rng.h",
+    "all": ["adjudicate.hip", "bitboard.h", "capi.hip", "engine.h", "kernels.h", "replay.h", "replay.hip", "resnet.hip", "rng.h",
             "schedule.h", "solver.h", "solver.hip", "timing.h", "tree.hip",
             "../../include/othello_mcts_amd.h", "../../include/othello_mcts_amd_experimental.h"],
 }

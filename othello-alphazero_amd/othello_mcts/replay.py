@@ -32,6 +32,7 @@ from .endgame import DEFAULT_NODE_LIMIT, _check_limits
 
 # sticky bits of the device counter block (include/othello_mcts_amd.h OAMD_REPLAY_*)
 FLAG_OVERFLOW, FLAG_NO_TARGETS, FLAG_TOO_LONG, FLAG_BAD_ID = 1, 2, 4, 8
+FLAG_SOLVER = 16  # an adjudicated game whose position the exact solver flagged (finished bit 6)
 
 # codes of the ``exact`` ring (include/othello_mcts_amd.h OAMD_REPLAY_EXACT_*); -64..64 is an exact score
 EXACT_UNKNOWN, EXACT_GAVE_UP = -128, -127
@@ -253,6 +254,8 @@ class ReplayBuffer:
             raise ValueError("The root node has not been expanded yet.")
         if flags & FLAG_TOO_LONG:
             raise RuntimeError("a game exceeded ReplayBuffer.max_moves")
+        if flags & FLAG_SOLVER:
+            raise RuntimeError("the exact solver flagged the position of an adjudicated game")
         if flags & FLAG_BAD_ID:
             raise IndexError("ReplayBuffer.gather: a sample id outside [0, 8 * size)")
 

@@ -28,6 +28,10 @@ import torch
 # written (unexpanded root), bit 3 the game's node pool overflowed
 FIN_NONE, FIN_DRAW, FIN_BLACK, FIN_WHITE = 0, 1, 2, 3
 FIN_NO_TARGETS, FIN_OVERFLOW = 4, 8
+# with adjudicate_empties > 0 (othello_mcts.adjudication): bit 5 the
+# game was ended at this move by the exact solver (bits 0-1 carry its exact
+# outcome), bit 6 the solver flagged the position (an error)
+FIN_ADJUDICATED, FIN_SOLVER_FLAG = 32, 64
 _OUTCOME_BLACK = {FIN_DRAW: 0.0, FIN_BLACK: 1.0, FIN_WHITE: -1.0}
 
 
@@ -74,6 +78,10 @@ class SelfPlayCollector:
         if bool(bad.any()):
             raise RuntimeError(f"node pool exhausted in game(s) {bad.nonzero().flatten().tolist()}: the search no "
                                "longer matches the reference; use a larger node_capacity")
+        flagged = (finished & FIN_SOLVER_FLAG) != 0
+        if bool(flagged.any()):
+            raise RuntimeError(f"the exact solver flagged the adjudicated position of game(s) "
+                               f"{flagged.nonzero().flatten().tolist()}")
         no_targets = (finished & FIN_NO_TARGETS) != 0
         if bool((no_targets & (actions >= 0)).any()):
             # the reference's self_play_data raises here (mcts.cpp:69-71)
@@ -109,7 +117,8 @@ class SelfPlayCollector:
 
 def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temperature: float = 1.0,
               opening_moves: int = 0, device: str | torch.device = "cpu",
-              moves_per_call: int = 16) -> dict[str, list[torch.Tensor]]:
+              moves_per_call: int = 16, adjudicate_empties: int = 0,
+              split: bool = False) -> dict[str, list[torch.Tensor]]:
     """Play until at least ``games`` games have completed across the batch (each
     slot restarts when its game ends) and return their samples in the
     reference's ``_self_play`` format (train.py:404-452). ``opening_moves=0``
@@ -123,14 +132,25 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
     uses, so the samples of the games completed by a given move are the same
     either way. The last call may play up to ``moves_per_call - 1`` moves past
     the one that completed the requested games (their finished games are
-    returned too)."""
+    returned too).
+
+    adjudicate_empties = K > 0: a game ends with the searched move that leaves
+    at most K empties, with the exact result of that position as its outcome
+    (othello_mcts.adjudication; ``split``: the split solver). The samples then
+    hold no position with K or fewer empties except the first searched move
+    after a restart whose opening already went that far."""
+    from .adjudication import check_adjudicate_empties
     from .native import resolve
+
+    check_adjudicate_empties(adjudicate_empties)
 
     col = SelfPlayCollector(batched.num_games, device=device)
     data = {"features": [], "policies": [], "values": []}
     native = moves_per_call > 1 and resolve(neural_net, batched.device.index, batched.config.history_size) is not None
     kw = dict(temperature_moves=temperature_moves, temperature=temperature, opening_moves=opening_moves,
               emit_targets=True)
+    if adjudicate_empties:
+        kw.update(adjudicate_empties=adjudicate_empties, split=split)
     while col.games_completed < games:
         if native:
             out = batched.selfplay_steps(neural_net, moves_per_call, keep_all=True, **kw)
@@ -146,4 +166,5 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
 
 
 __all__ = ["SelfPlayCollector", "self_play", "outcome_for_black", "value_targets_from_outcome",
-           "FIN_NO_TARGETS", "FIN_OVERFLOW", "FIN_NONE", "FIN_DRAW", "FIN_BLACK", "FIN_WHITE"]
+           "FIN_NO_TARGETS", "FIN_OVERFLOW", "FIN_NONE", "FIN_DRAW", "FIN_BLACK", "FIN_WHITE", "FIN_ADJUDICATED",
+           "FIN_SOLVER_FLAG"]

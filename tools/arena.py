@@ -11,6 +11,12 @@ the reference's estimate_elo / save_pgn) as JSON.
 
 Usage (GPU box):
   python tools/arena.py NET_A NET_B [--games 256] [--sims 800] [--opening-plies 4] [--out FILE.json]
+                        [--adjudicate K [--split]]
+
+--adjudicate K: a match ends at the ply that leaves at most K empties, with the
+exact result of that position (Arena.play(adjudicate_empties=K), DESIGN.md §16;
+--split: by the split solver). The JSON carries margin (seen from black) and
+adjudicated per match.
 """
 
 import argparse
@@ -58,6 +64,8 @@ def main() -> None:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--adjudicate", type=int, default=0, metavar="K")
+    ap.add_argument("--split", action="store_true")
     a = ap.parse_args()
 
     live_a, live_b = a.net_a.startswith("live:"), a.net_b.startswith("live:")
@@ -75,7 +83,8 @@ def main() -> None:
     c0 = [m.engine.work_counters() for m in (arena.a, arena.b)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = arena.play(net_a, net_b, temperature_moves=a.temperature_moves)
+    res = arena.play(net_a, net_b, temperature_moves=a.temperature_moves, adjudicate_empties=a.adjudicate,
+                     split=a.split)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     c1 = [m.engine.work_counters() for m in (arena.a, arena.b)]
@@ -90,10 +99,13 @@ def main() -> None:
         "wins_a": w, "draws": d, "losses_a": lost, "score_a": res.score_a(), "plies": res.plies, "moves": moves,
         "wall_s": wall, "simulations": sims, "nn_rows": evals, "simulations_per_s": sims / wall,
         "nn_rows_per_s": evals / wall, "device": torch.cuda.get_device_name(0),
+        "adjudicate_empties": a.adjudicate, "split": a.split, "margin": res.margin.tolist(),
+        "adjudicated": res.adjudicated.tolist(), "mean_margin_a": float(res.margin_a().float().mean()),
         "records": res.records(a.net_a, a.net_b),
     }
     print(f"A {a.net_a} vs B {a.net_b}: {a.games} matches, {a.sims} simulations per move")
-    print(f"W/D/L (A) {w}/{d}/{lost}  score {out['score_a']:.3f}  plies {res.plies}  moves {moves}")
+    print(f"W/D/L (A) {w}/{d}/{lost}  score {out['score_a']:.3f}  plies {res.plies}  moves {moves}  "
+          f"adjudicated {int(res.adjudicated.sum())}  mean margin (A) {out['mean_margin_a']:+.2f}")
     print(f"wall {wall:.2f} s  {sims / wall / 1e6:.3f} M simulations/s  {evals / wall / 1e6:.3f} M NN rows/s")
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)

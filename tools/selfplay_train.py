@@ -12,7 +12,8 @@ trained net's are (trees of a trained net concentrate and
 descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
-Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds] [packed [exact=K [split]]]
+Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds]
+                 [packed [exact=K]] [adjudicate=K] [split]
 
 packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
 million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
@@ -25,6 +26,18 @@ as their value target (ReplayBuffer.relabel_endgames). The
 iteration's log line gains relabel_ms (device events around the call) and the
 buffer's relabel_stats. split (with exact=K): the split solver does the
 relabelling (relabel_endgames(split=True)).
+
+adjudicate=K: self-play games end at the searched move that leaves at most K
+empties, with the exact result of that position (selfplay_steps(...,
+adjudicate_empties=K); split: by the split solver). The log line
+gains adjudicated (games the solver ended in the iteration), resolve_ms (device
+events around the resolve step, mean over the iteration's selfplay_steps
+calls; reading them waits for each call, a host wait the K = 0 run does not
+have) and resolve_share (their sum over the self-play phase).
+
+new_positions (packed) is the ring head's advance, valid while one iteration
+stores fewer positions than the ring holds; new_games / selfplay_s and
+new_positions / selfplay_s are the games/s and stored positions/s of a phase.
 """
 
 import json
@@ -93,9 +106,11 @@ def main():
     exact = [int(w[6:]) for w in sys.argv[5:] if w.startswith("exact=")]
     if exact and not packed:
         raise SystemExit("exact=K needs the packed buffer")
+    adjudicate = [int(w[11:]) for w in sys.argv[5:] if w.startswith("adjudicate=")]
+    K = adjudicate[0] if adjudicate else 0
     split = "split" in sys.argv[5:]
-    if split and not exact:
-        raise SystemExit("split needs exact=K")
+    if split and not (exact or K):
+        raise SystemExit("split needs exact=K or adjudicate=K")
     moves_per_iter = 64
     torch.manual_seed(0)
     dev = torch.device("cuda", 0)
@@ -116,10 +131,19 @@ def main():
     gen = torch.Generator().manual_seed(1)
     for it in range(iterations):
         t0 = time.time()
-        games0 = buf.games_completed
+        games0, size0 = buf.games_completed, (buf.head if packed else buf.size)
+        adjudicated = None
+        resolve_ms = []
+        if K and it == 0:
+            b.engine.adjudicate_ms()  # switches the resolve step's events on
         for _ in range(moves_per_iter // 16):  # 16 moves per call: bounded output buffers
             o = b.selfplay_steps(native, 16, temperature_moves=12, opening_moves=0, emit_targets=True,
-                                 keep_all=True)
+                                 keep_all=True, adjudicate_empties=K, split=split and K > 0)
+            if K:
+                n_adj = ((o["finished"] & 32) != 0).sum()  # stays on the device until the phase is over
+                adjudicated = n_adj if adjudicated is None else adjudicated + n_adj
+                o = {k: v for k, v in o.items() if k != "margin"}
+                resolve_ms.append(b.engine.adjudicate_ms()[0])
             if packed:
                 buf.add(o)
             else:
@@ -128,6 +152,11 @@ def main():
         torch.cuda.synchronize()
         t1 = time.time()
         selfplay_s = round(t1 - t0, 2)
+        adj = {}
+        if K:
+            adj = {"adjudicated": int(adjudicated), "resolve_ms": round(sum(resolve_ms) / len(resolve_ms), 3),
+                   "resolve_ms_calls": [round(x, 3) for x in resolve_ms],
+                   "resolve_share": round(sum(resolve_ms) / 1e3 / max(t1 - t0, 1e-9), 5)}
         relabel = {}
         if exact:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -149,8 +178,8 @@ def main():
         om.refresh_native(native, model)
         torch.cuda.synchronize()
         rec = {"iteration": it, "games": buf.games_completed, "new_games": buf.games_completed - games0,
-               "samples": n, "selfplay_s": selfplay_s, "train_s": round(time.time() - t1, 2),
-               **relabel, **{k: round(v, 4) for k, v in losses.items()}}
+               "samples": n, "new_positions": ((buf.head - size0) % buf.capacity if packed else (buf.size - size0) // 8),
+               "selfplay_s": selfplay_s, "train_s": round(time.time() - t1, 2), **adj, **relabel, **{k: round(v, 4) for k, v in losses.items()}}
         log.append(rec)
         print(json.dumps(rec), flush=True)
         if time.time() - t_start > (float(sys.argv[4]) if len(sys.argv) > 4 else 900.0):
@@ -162,7 +191,9 @@ def main():
                                                     "moves_per_iteration": moves_per_iter,
                                                     "buffer": "packed" if packed else "fp32",
                                                     "exact_max_empties": exact[0] if exact else None,
-                                                    "exact_split": split}, indent=1))
+                                                    "exact_split": split and bool(exact),
+                                                    "adjudicate_empties": K, "adjudicate_split": split and K > 0},
+                                                   indent=1))
 
 
 if __name__ == "__main__":

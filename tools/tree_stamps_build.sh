@@ -13,6 +13,7 @@ $CXX $EXACT $NOSCALAR -c $CS/tree.hip -o abv/ts/tree.o &
 $CXX $EXACT -c $CS/capi.hip -o abv/ts/capi.o &
 $CXX $EXACT -c $CS/replay.hip -o abv/ts/replay.o &  # capi.hip calls the launchers of every unit of build.py's UNITS
 $CXX -c $CS/solver.hip -o abv/ts/solver.o &
+$CXX -c $CS/adjudicate.hip -o abv/ts/adjudicate.o &
 $CXX $RF -c $CS/resnet.hip -o abv/ts/resnet.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abv/ts/liboamd.so abv/ts/*.o
