@@ -1,8 +1,8 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
   liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip, adjudicate.hip) + the C ABI
-                           (capi.hip),
-                           hipcc --offload-arch=gfx950
+                           (capi.hip and, by subsystem, capi_net.hip, capi_play.hip, capi_data.hip; capi_version.hip
+                           carries the source hashes), hipcc --offload-arch=gfx950
   _othello_mcts_impl*.so   pybind11 host layer (pybind_module.cpp) over the C ABI
 
 Both land in othello-alphazero_amd/othello_mcts/ (git-ignored, shipped to the
@@ -29,8 +29,10 @@ ARCH = os.environ.get("OAMD_ARCH", "gfx950")
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", str(CSRC), "-I", str(INCLUDE),
           "-Wall", "-Wno-unused-function", "-fno-gpu-rdc", *os.environ.get("OAMD_EXTRA_FLAGS", "").split()]
-# tree.hip / rng.h / capi.hip tables must reproduce the reference's float
-# arithmetic bit for bit: no FMA contraction, IEEE division and sqrt.
+# tree.hip / rng.h, capi.hip's tables and capi_net.hip's weight fold must
+# reproduce the reference's float arithmetic bit for bit: no FMA contraction,
+# IEEE division and sqrt. The C ABI's other host units share inline host code
+# with those two (capi_internal.h), so they are built the same way.
 EXACT = ["-ffp-contract=off", "-fno-fast-math"]
 # tree.hip's kernels read statistics, links and game state that the same wave
 # has just written with vector stores (ordered by a wavefront fence, tree.hip
@@ -40,6 +42,10 @@ NO_SCALAR_LOADS = ["-mllvm", "-amdgpu-scalarize-global-loads=false"]
 UNITS = {
     "tree.hip": EXACT + NO_SCALAR_LOADS,
     "capi.hip": EXACT,
+    "capi_net.hip": EXACT,
+    "capi_play.hip": EXACT,
+    "capi_data.hip": EXACT,
+    "capi_version.hip": [],
     # packed replay buffer: its value targets are SampleBuffer's, bit for bit
     "replay.hip": EXACT,
     # accumulators and fragments in arch VGPRs: the default heuristic parks the
@@ -160,7 +166,7 @@ def newer(out: Path, deps: list[Path]) -> bool:
 
 def source_hash_defines() -> list[str]:
     """-D flags carrying the source hashes (othello_mcts/provenance.py) into
-    capi.hip, so the library reports what it was built from."""
+    capi_version.hip, so the library reports what it was built from."""
     sys.path.insert(0, str(PKG))
     try:
         import provenance
@@ -180,10 +186,11 @@ def build(jobs: int = 4, force: bool = False) -> None:
         src = CSRC / unit
         obj = BUILD / (unit + ".o")
         objs.append(obj)
-        # capi.hip carries the hashes of every source: rebuilt when any changes
-        deps = all_srcs if unit == "capi.hip" else [src, *headers]
+        # the version unit carries the hashes of every source: rebuilt when any changes
+        versioned = unit == "capi_version.hip"
+        deps = all_srcs if versioned else [src, *headers]
         if force or not newer(obj, [*deps, Path(__file__)]):
-            todo.append([HIPCC, *COMMON, *extra, *(hashes if unit == "capi.hip" else []), "-c", str(src),
+            todo.append([HIPCC, *COMMON, *extra, *(hashes if versioned else []), "-c", str(src),
                          "-o", str(obj)])
     with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
         list(ex.map(run, todo))

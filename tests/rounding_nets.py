@@ -12,7 +12,7 @@ round-to-nearest-even, at any layer and in any geometry. One wrong rounding
 moves a logit by at least one `step`; exact_nets.compare's quarter-step
 criterion applies unchanged and no measured tolerance is involved.
 
-The kernel's numeric spec, as read from csrc/capi.hip (oamd_net_load_state)
+The kernel's numeric spec, as read from csrc/capi_net.hip (oamd_net_load_state)
 and csrc/resnet.hip (pack_relu, the accumulator start, heads()):
   * fold: scale = gamma / sqrt(var + 1e-5) in double; weight (float)(W scale),
     then rounded to the dtype (RNE); bias (float)((b - mu) scale + beta), kept

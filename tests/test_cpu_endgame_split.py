@@ -453,3 +453,24 @@ def test_standalone_check_runs_clean_under_the_sanitizers(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "0 failures" in r.stdout and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr
     assert re.search(r"[1-9]\d* with L = 64", r.stdout)
+
+
+def test_host_resources_check_runs_clean_under_the_sanitizers(tmp_path):
+    """tools/host_resources_check.cpp, a program of its own, built by the host
+    compiler alone with -fsanitize=address,undefined: csrc/host_resources.h
+    (the owners of the host layer's device resources and the engine's resource
+    sets) over counting HIP stubs. Every creating call of one scenario fails
+    once: the call reports it, every set still holds what it held, the retry
+    succeeds, and the run ends in the state of the run without a failure;
+    nothing is live after destruction or released twice; streams and events
+    are created in the order the schedules were measured with. No Python runs
+    under a sanitizer."""
+    hipcc = Path(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))  # build.py's compiler: its headers
+    exe = tmp_path / "host_resources_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-D__HIP_PLATFORM_AMD__",
+                    "-I", str(hipcc.parent.parent / "include"), "-I", str(PKG / "csrc"),
+                    str(ROOT / "tools" / "host_resources_check.cpp"), "-o", str(exe)], check=True, capture_output=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "0 failures" in r.stdout and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr
+    assert re.search(r"([1-9]\d*) creating calls, \1 runs with one of them failing", r.stdout)

@@ -597,3 +597,41 @@ def test_tree_work_counters_price_the_byte_model(om):
     assert la1 - la0 >= steps  # >= one launch per round (2 pipeline groups: 2 per round + final backups)
     numerics.record("tree work counters", f"levels={lv1 - lv0} scanned={sc1 - sc0} expansions={ex1 - ex0} "
                                           f"children={cr1 - cr0} launches={la1 - la0} sims={sims} evals={evals}")
+
+
+def test_set_config_grows_and_shrinks_like_a_fresh_engine(om):
+    """oamd_engine_set_config replaces the per-row buffers when the new shape
+    (rows = G x T x B) does not fit them and keeps them when it does. An engine
+    that searched at T=1 x B=4, grew to T=2 x B=8, shrank back and grew again
+    must search, after a reset with the same seed, exactly like an engine
+    created with that config: root visits and Q of both games, bit for bit."""
+    from othello_mcts.synthetic import alphazero_state_dict
+
+    net = om.NativeNet(alphazero_state_dict(4, 5, 128, 1, 32), device=0)
+    small = dict(history_size=2, num_simulations=32, num_threads=1, batch_size=4)
+    large = dict(history_size=2, num_simulations=32, num_threads=2, batch_size=8)
+    SEED = 77
+
+    def engine(kw):
+        return om.BatchedMCTS(2, **kw, seed=5, node_capacity=1 << 12)
+
+    def configure(b, kw):
+        b.config.num_threads, b.config.batch_size = kw["num_threads"], kw["batch_size"]
+        b.engine.set_config(b.config)
+
+    def searched(b):
+        b.reset(-1, SEED)
+        sims, _ = b.search(net)
+        assert sims == 2 * 32
+        v, q = b.root_stats()
+        assert b.engine.status() == (0, 0)
+        return v.cpu().numpy(), q.cpu().numpy().view(np.uint32)
+
+    fresh = {name: searched(engine(kw)) for name, kw in (("small", small), ("large", large))}
+    a = engine(small)
+    a.search(net)
+    for step, (name, kw) in enumerate((("large", large), ("small", small), ("large", large))):
+        configure(a, kw)
+        v, q = searched(a)
+        np.testing.assert_array_equal(v, fresh[name][0], err_msg=f"visits after set_config #{step} ({name})")
+        np.testing.assert_array_equal(q, fresh[name][1], err_msg=f"Q bits after set_config #{step} ({name})")

@@ -1,5 +1,5 @@
 """Zero-slack tests of the fused ResNet's 16-bit roundings (csrc/resnet.hip's
-pack_relu epilogue and accumulator start, csrc/capi.hip's weight loader) on
+pack_relu epilogue and accumulator start, csrc/capi_net.hip's weight loader) on
 the rounding probe nets of tests/rounding_nets.py: nets whose fp32 sums are
 exact in any order but whose layer results do not fit bf16 / fp16, so what
 the kernel stores is one specific rounded number that the integer reference

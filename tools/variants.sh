@@ -6,8 +6,8 @@
 # every unit of the working tree built with the flags;
 # a path = that resnet.hip with the tree's other objects; tree=PATH = that
 # tree.hip with the working tree's other units; @REV = all of
-# csrc/ and include/ at git revision REV (capi.hip packs the weights, so a
-# variant that changes the packing must bring its own capi). The units and
+# csrc/ and include/ at git revision REV (capi_net.hip packs the weights, so a
+# variant that changes the packing must bring its own C ABI units). The units and
 # their flags are build.py's UNITS (resnet.hip's from RF). Built into
 # abv/<name>/liboamd.so (the pybind layer binds the C ABI, not the variant).
 set -eu
