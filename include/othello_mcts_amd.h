@@ -267,6 +267,8 @@ typedef struct oamd_selfplay_config {
  *   0 game continues, 1 draw, 2 black won, 3 white won (the game ended with
  *   this move and restarted); bit 2 = the root was unexpanded, no targets were
  *   written (the move was uniform); bit 3 = the game's node pool overflowed;
+ *   bit 7 (128) = the move followed a fast search of a playout cap (below): it
+ *   was played, but no targets were written;
  *   features_dev (G, 8, 1+2H, 8, 8) and policy_dev (G, 8, 65) targets. */
 int oamd_engine_selfplay_move(oamd_engine *e, const oamd_selfplay_config *cfg,
                               int32_t *actions_dev, int32_t *finished_dev, float *features_dev,
@@ -312,6 +314,51 @@ int oamd_engine_selfplay_steps_adjudicated(oamd_engine *e, oamd_net *net, const 
                                            int32_t n_moves, int32_t per_move_outputs, int32_t *actions_dev,
                                            int32_t *finished_dev, float *features_dev, float *policy_dev,
                                            int32_t max_empties, int32_t split, int32_t *margin_dev);
+
+/* Playout cap randomization (KataGo, Wu 2019, section 3.1; DESIGN.md §17;
+ * opt-in, off by default). With a cap set, the search of a game at ply `ply`
+ * (moves since its last restart or opening) is a FULL one - num_simulations,
+ * root noise, its move recorded as a training target - when
+ * oamd_playout_cap_is_full(game key, ply, full_probability) says so, which
+ * happens with probability full_probability. Otherwise it is a FAST one:
+ * fast_simulations (rounded up to whole batches like num_simulations), no
+ * root Dirichlet noise (no noise events are consumed), and the self-play
+ * move that follows it is chosen and applied as ever but writes no targets
+ * and reports finished bit 7 (128). The draw consumes no event of the game's
+ * random stream, and the tree is reused across moves as ever. It applies to
+ * every search of the engine: oamd_engine_search, the step API
+ * (oamd_engine_search_begin still returns the full step count; the rows of a
+ * game on a fast search are simply not flagged after its steps) and
+ * oamd_engine_selfplay_steps. The arena does not use it and rejects an engine
+ * that has it set. */
+typedef struct oamd_playout_cap {
+    float full_probability;   /* in (0, 1]; 1 = every search is full */
+    int32_t fast_simulations; /* in 1..num_simulations */
+} oamd_playout_cap;
+/* cap = NULL: off. OAMD_INVALID_ARGUMENT: a value out of range; an engine of
+ * one game with more than one thread (the thread-split schedule). While a
+ * cap is set, oamd_engine_set_config rejects a config it does not fit. */
+int oamd_engine_set_playout_cap(oamd_engine *e, const oamd_playout_cap *cap);
+/* The full / fast draw (host): 1 = full. The key is oamd_engine_game_key's. */
+int oamd_playout_cap_is_full(uint64_t game_key, int32_t ply, float full_probability);
+/* oamd_engine_selfplay_steps_adjudicated with a work budget per game in place
+ * of a move count (sim_budget = 0 IS that call, max_moves its n_moves).
+ * sim_budget > 0: max_moves is the number of output slices and the most moves
+ * a game plays in the call; a game stops after the move whose search brought
+ * the nominal simulations (batches per thread x num_threads x batch_size) of
+ * the searches it started in this call to sim_budget or more. A game always
+ * finishes the search it started, so it overshoots by less than one search.
+ * Move i of a game goes to slice i; every slice of every game is first filled
+ * with action -1 and finished 0 ("nothing played"), so a game's played moves
+ * are a prefix of its slices. With adjudication the slots nothing was played
+ * into have margin INT32_MIN. OAMD_INVALID_ARGUMENT: sim_budget > 0 with
+ * per_move_outputs = 0, with the free-running schedule switched off, or on an
+ * engine of one game with more than one thread. */
+int oamd_engine_selfplay_steps_budget(oamd_engine *e, oamd_net *net, const oamd_selfplay_config *cfg,
+                                      int32_t max_moves, int32_t sim_budget, int32_t per_move_outputs,
+                                      int32_t *actions_dev, int32_t *finished_dev, float *features_dev,
+                                      float *policy_dev, int32_t max_empties, int32_t split,
+                                      int32_t *margin_dev);
 /* Reset every game to a random opening. */
 int oamd_engine_random_openings(oamd_engine *e, int32_t max_moves, uint64_t seed);
 /* The random-stream key of a game (DESIGN.md "Random streams"). */

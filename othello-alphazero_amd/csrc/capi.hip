@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "capi_internal.h"
+#include "rng.h"
 
 using namespace oamd;
 
@@ -180,6 +181,8 @@ int oamd_engine_destroy(oamd_engine* e) {
 int oamd_engine_set_config(oamd_engine* e, const oamd_search_config* cfg) {
     int rc = validate_config(cfg);
     if (rc) return rc;
+    if (const char* why = e->playout_cap_conflict(*cfg))
+        return fail(OAMD_INVALID_ARGUMENT, std::string(why) + " (oamd_engine_set_playout_cap(e, NULL) switches it off)");
     DeviceGuard dg(e->device);
     const bool tabs = cfg->c_puct_base != e->cfg.c_puct_base || cfg->c_puct_init != e->cfg.c_puct_init;
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -831,8 +834,16 @@ int oamd_engine_apply_actions(oamd_engine* e, const int32_t* actions_dev) {
 // drains the queue), is 0. The
 // tail chunks' ResNet launches use the small looping grid (extra_grid): only
 // lagging games have rows then. Returns once the last chunk is enqueued.
+//
+// Work budget (sim_budget > 0): n_moves is the slice count and
+// the most moves of a game; every game stops after the move whose search used
+// its budget of nominal simulations up (k_free_begin). A game runs one batch
+// per thread and round, so the budget lasts ceil(sim_budget / L) rounds plus
+// the first search's extra one: those are the base chunks, and the tail chunks
+// pick up the games that lag or overshoot (by less than one search).
 static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const SelfplayParams& sp, int n_moves,
-                               int per_move, int32_t* actions, int32_t* finished, float* feat, float* pol) {
+                               int per_move, int32_t* actions, int32_t* finished, float* feat, float* pol,
+                               int sim_budget) {
     if (int rc = e->ensure_remaining()) return rc;
     const GroupPlan P = plan_groups(e);
     const int K = P.K;
@@ -851,12 +862,17 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const SelfplayPara
         for (int k = 0; k < K; ++k) {
             HIPCHK(hipMemsetAsync(e->rowcount.get() + 2 * k, 0, 2 * sizeof(int32_t), P.st[k]));
             HIPCHK(hipMemsetAsync(e->remaining.dev.get() + k, 0, sizeof(int32_t), P.st[k]));
-            launch_free_begin(E, P.g0[k], P.ng[k], n_moves, e->remaining.dev.get() + k, actions, finished, per_move, P.st[k]);
+            launch_free_begin(E, P.g0[k], P.ng[k], n_moves, e->remaining.dev.get() + k, actions, finished, per_move,
+                              sim_budget, P.st[k]);
         }
         bool gdone[kMaxPipeline] = {};
-        const int64_t base_rounds = n_moves > 0 ? (int64_t)n_moves * steps + 1 : 0;
+        const int64_t move_rounds = (int64_t)n_moves * steps + 1;
+        const int64_t base_rounds =
+            n_moves <= 0 ? 0 : (sim_budget > 0 ? std::min(move_rounds, ((int64_t)sim_budget + E.L - 1) / E.L + 1) : move_rounds);
         // a round completes at least one batch of every game still playing (or
-        // its move): a generous bound that only a kernel fault could exceed
+        // its move): a generous bound that only a kernel fault could exceed.
+        // Under a budget a game still plays at most n_moves moves of at most
+        // `steps` batches per thread each, so the same bound holds.
         const int64_t max_rounds = base_rounds + (int64_t)n_moves * ((int64_t)T * steps + 2) + 4 * oamd_engine::kFreeTailRounds;
         for (int64_t chunk = 0; n_moves > 0; ++chunk) {
             int R;
@@ -903,7 +919,8 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const SelfplayPara
                     int* cnt = e->rowcount.get() + 2 * k;
                     if (ev) HIPCHK(hipEventRecord(ev[0].get(), sk));
                     launch_tree_free(E, sk, P.g0[k], P.ng[k], B, cnt + (r & 1), cnt + ((r + 1) & 1), budget, timed, sp,
-                                     n_moves, per_move, actions, finished, feat, pol, e->remaining.dev.get() + k);
+                                     n_moves, per_move, actions, finished, feat, pol, e->remaining.dev.get() + k,
+                                     sim_budget);
                     if (ev) HIPCHK(hipEventRecord(ev[1].get(), sk));
                     // a chain's first launch of the call has no token to wait for
                     const bool first = r == 0 && k < std::min(e->nn_chains, K);
@@ -932,9 +949,37 @@ static int selfplay_steps_free(oamd_engine* e, oamd_net* net, const SelfplayPara
     const int jrc = join_groups(e, P);
     e->end_search();
     if (rc) return rc;
-    e->grouped_searches += n_moves;
+    // (under a budget: the full searches it pays for; the games' own counts differ)
+    e->grouped_searches += sim_budget > 0 ? std::min<int64_t>(n_moves, ((int64_t)sim_budget + (int64_t)steps * E.L - 1) / ((int64_t)steps * E.L)) : n_moves;
     e->grouped_rounds += round;
     return jrc;
+}
+
+int oamd_engine_set_playout_cap(oamd_engine* e, const oamd_playout_cap* cap) {
+    if (!cap) {
+        e->cap_p = 1.0f;
+        e->cap_fast = 0;
+        return OAMD_OK;
+    }
+    if (!(cap->full_probability > 0.0f && cap->full_probability <= 1.0f))
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "Expected 0 < full_probability <= 1, but got " + std::to_string(cap->full_probability) + ".");
+    if (cap->fast_simulations < 1 || cap->fast_simulations > e->cfg.num_simulations)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 1 <= fast_simulations <= num_simulations (" +
+                                               std::to_string(e->cfg.num_simulations) + "), but got " +
+                                               std::to_string(cap->fast_simulations) + ".");
+    if (thread_split_shape(e->G, e->cfg.num_threads))
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "the playout cap does not run on the single-game thread-split schedule (num_games = 1, "
+                    "num_threads > 1)");
+    e->cap_p = cap->full_probability;
+    e->cap_fast = cap->fast_simulations;
+    e->end_search();
+    return OAMD_OK;
+}
+
+int oamd_playout_cap_is_full(uint64_t game_key, int32_t ply, float full_probability) {
+    return playout_cap_full(game_key, ply, full_probability) ? 1 : 0;
 }
 
 int oamd_engine_set_free_running(oamd_engine* e, int32_t enable) {
@@ -946,7 +991,7 @@ int oamd_engine_set_free_running(oamd_engine* e, int32_t enable) {
 // carries the adjudication fields (pending slots laid out like `finished`)
 static int selfplay_steps_enqueue(oamd_engine* e, oamd_net* net, const SelfplayParams& sp, int32_t n_moves,
                                   int32_t per_move_outputs, int32_t* actions_dev, int32_t* finished_dev,
-                                  float* features_dev, float* policy_dev) {
+                                  float* features_dev, float* policy_dev, int32_t sim_budget) {
     const int G = e->G, C = 1 + 2 * e->cfg.history_size;
     // move i's outputs: the i-th slice of per-move buffers, or the same G-game buffers every move
     auto out = [&](int i, auto* p, int64_t per_game) { return p ? p + (per_move_outputs ? (int64_t)i * G * per_game : 0) : p; };
@@ -960,8 +1005,10 @@ static int selfplay_steps_enqueue(oamd_engine* e, oamd_net* net, const SelfplayP
     if (!split && e->free_running) {
         if (int rc = e->pipe.ensure(P.K, P.K)) return rc;
         return selfplay_steps_free(e, net, sp, n_moves, per_move_outputs, actions_dev, finished_dev, features_dev,
-                                   policy_dev);
+                                   policy_dev, sim_budget);
     }
+    if (sim_budget > 0)  // (checked by the caller before anything was enqueued)
+        return fail(OAMD_INVALID_ARGUMENT, "sim_budget needs the free-running schedule");
     if (split || P.K == 1) {  // one stream: the plain sequence of calls
         for (int i = 0; i < n_moves; ++i) {
             if (int rc = oamd_engine_search(e, net, nullptr, nullptr)) return rc;
@@ -999,12 +1046,25 @@ static int selfplay_steps_enqueue(oamd_engine* e, oamd_net* net, const SelfplayP
     return OAMD_OK;
 }
 
-int oamd_engine_selfplay_steps_adjudicated(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg,
-                                           int32_t n_moves, int32_t per_move_outputs, int32_t* actions_dev,
-                                           int32_t* finished_dev, float* features_dev, float* policy_dev,
-                                           int32_t max_empties, int32_t split, int32_t* margin_dev) {
+// Adjudication under a budget: the resolve step walks all max_moves x G
+// pending slots. A slot no move was played into is still all-zero from
+// adjudicate_begin's memset (no discs), which adjudicate.hip treats as empty:
+// it is told from a played slot by the pending position, not by `finished`.
+int oamd_engine_selfplay_steps_budget(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg,
+                                      int32_t max_moves, int32_t sim_budget, int32_t per_move_outputs,
+                                      int32_t* actions_dev, int32_t* finished_dev, float* features_dev,
+                                      float* policy_dev, int32_t max_empties, int32_t split, int32_t* margin_dev) {
+    const int32_t n_moves = max_moves;
     if (int rc = adjudicate_checks(max_empties, finished_dev)) return rc;
     if (n_moves < 0) return fail(OAMD_INVALID_ARGUMENT, "n_moves must be >= 0");
+    if (sim_budget < 0) return fail(OAMD_INVALID_ARGUMENT, "sim_budget must be >= 0");
+    if (sim_budget > 0 && !per_move_outputs)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "sim_budget needs per_move_outputs (games play different numbers of moves in the call)");
+    if (sim_budget > 0 && (e->thread_split() || thread_split_shape(e->G, e->cfg.num_threads) || !e->free_running))
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "sim_budget needs the free-running schedule (oamd_engine_set_free_running, and more than one "
+                    "game or one thread)");
     if (max_empties > 0 && n_moves > 1 && !per_move_outputs)
         return fail(OAMD_INVALID_ARGUMENT,
                     "adjudication needs per_move_outputs when n_moves > 1 (a move would overwrite the pending "
@@ -1016,10 +1076,18 @@ int oamd_engine_selfplay_steps_adjudicated(oamd_engine* e, oamd_net* net, const 
     const int64_t n = max_empties > 0 ? (int64_t)n_moves * e->G : 0;
     if (int rc = adjudicate_begin(e, n, max_empties, split != 0, &sp)) return rc;
     if (int rc = selfplay_steps_enqueue(e, net, sp, n_moves, per_move_outputs, actions_dev, finished_dev,
-                                        features_dev, policy_dev))
+                                        features_dev, policy_dev, sim_budget))
         return rc;
     // after the groups have joined the caller's stream
     return adjudicate_resolve(e, n, max_empties, split != 0, finished_dev, margin_dev, false);
+}
+
+int oamd_engine_selfplay_steps_adjudicated(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg,
+                                           int32_t n_moves, int32_t per_move_outputs, int32_t* actions_dev,
+                                           int32_t* finished_dev, float* features_dev, float* policy_dev,
+                                           int32_t max_empties, int32_t split, int32_t* margin_dev) {
+    return oamd_engine_selfplay_steps_budget(e, net, cfg, n_moves, 0, per_move_outputs, actions_dev, finished_dev,
+                                             features_dev, policy_dev, max_empties, split, margin_dev);
 }
 
 int oamd_engine_selfplay_steps(oamd_engine* e, oamd_net* net, const oamd_selfplay_config* cfg, int32_t n_moves,

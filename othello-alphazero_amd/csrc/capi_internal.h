@@ -155,6 +155,21 @@ struct oamd_engine {
                                 "free-running slots");
     }
     oamd::AdjudicateWorkspace adj;  // oamd_engine_selfplay_*_adjudicated, oamd_arena_*_adjudicated
+    // playout cap randomization (oamd_engine_set_playout_cap):
+    // cap_fast = 0 is off; else a search is full with probability cap_p and
+    // runs cap_fast simulations without root noise otherwise
+    float cap_p = 1.0f;
+    int cap_fast = 0;
+    bool playout_cap() const { return cap_fast > 0; }
+    // why a search config cannot carry the current cap (nullptr: it can)
+    const char* playout_cap_conflict(const oamd_search_config& c) const {
+        if (!playout_cap()) return nullptr;
+        if (thread_split_shape(G, c.num_threads))
+            return "the playout cap does not run on the single-game thread-split schedule (num_games = 1, "
+                   "num_threads > 1)";
+        if (cap_fast > c.num_simulations) return "the playout cap's fast_simulations exceeds num_simulations";
+        return nullptr;
+    }
     // workgroups of an extra round's ResNet launch (0 = the regular grid)
     int extra_grid = 128;
     int step_phase = 0;  // 1 = a selected round awaits its backup (step API)
@@ -272,6 +287,8 @@ struct oamd_engine {
         E.steps = steps();
         E.B = cfg.batch_size;
         E.terminal_skip = exact_interleaving ? 1 : 0;
+        E.fast_steps = playout_cap() ? search_steps(cap_fast, L()) : 0;
+        E.full_probability = cap_p;
         return E;
     }
 };

@@ -135,6 +135,9 @@ static int arena_checks(const oamd_engine* a, const oamd_engine* b) {
         return fail(OAMD_INVALID_ARGUMENT, "arena: engines hold different numbers of games (" + std::to_string(a->G) +
                                                " and " + std::to_string(b->G) + ")");
     if (a->stream != b->stream) return fail(OAMD_INVALID_ARGUMENT, "arena: engines on different streams");
+    // matches are played with full searches
+    if (a->playout_cap() || b->playout_cap())
+        return fail(OAMD_INVALID_ARGUMENT, "arena: an engine has a playout cap set (the arena does not use it)");
     return OAMD_OK;
 }
 

@@ -50,7 +50,8 @@ struct GameState {
     int32_t moves_left;  // free-running self-play (k_tree_free): moves this game still plays in the call
     int32_t fresh;       // ... 1: its next round starts a new search
     int32_t arena;       // arena match (k_arena_begin): 0 none, 1 net A plays black, 2 net A plays white
-    int32_t pad;
+    int32_t sims_left;   // free-running call with a work budget: nominal simulations the game
+                         // may still start searches for in this call (0 with no budget)
 };
 static_assert(sizeof(GameState) == 128, "GameState layout");
 
@@ -62,6 +63,9 @@ constexpr int32_t kArenaDesync = 16;
 // solver flagged the position (cannot happen for an engine position)
 constexpr int32_t kFinAdjudicated = 32;
 constexpr int32_t kFinSolverFlag = 64;
+// ... and of the self-play driver under a playout cap: the move
+// followed a fast search, so no targets were written for it
+constexpr int32_t kFinFast = 128;
 
 // Packed NN input row (FW uint64 words): word 0 = meta, then (p1, p2) of the
 // leaf and its H-1 nearest ancestors, untransformed. meta bit 0 = player - 1,
@@ -97,6 +101,11 @@ struct EngineView {
     int32_t B;         // batch_size (leaves per virtual thread and batch)
     int32_t terminal_skip;  // 1: an all-terminal batch is backed up at once and its thread selects
                             // again (the reference's interleaving); 0: it waits for its round
+    // playout cap randomization: 0 = off; else a search that
+    // playout_cap_full (rng.h) calls fast runs fast_steps batches per virtual
+    // thread with no root noise
+    int32_t fast_steps;
+    float full_probability;
 };
 
 }  // namespace oamd

@@ -65,12 +65,13 @@ void launch_arena_move(const EngineView& EA, const EngineView& EB, const Selfpla
 // group to play n_moves moves starting with a fresh search and counts them in
 // *remaining; each round runs one search round per game, a game's move in the
 // round its search completes, and its next search's first round after it.
-// *remaining must be zeroed before begin (stream order).
+// *remaining must be zeroed before begin (stream order). sim_budget > 0 (with
+// per_move): the work budget of k_free_begin's comment, n_moves = the slices.
 void launch_free_begin(const EngineView& E, int g0, int ng, int n_moves, int32_t* remaining, int32_t* actions,
-                       int32_t* finished, int per_move, hipStream_t s);
+                       int32_t* finished, int per_move, int sim_budget, hipStream_t s);
 void launch_tree_free(const EngineView& E, hipStream_t s, int g0, int ng, int B, int* cnt_add, int* cnt_reset,
                       int budget, bool timed, const SelfplayParams& sp, int n_moves, int per_move, int32_t* actions,
-                      int32_t* finished, float* feat, float* pol, int32_t* remaining);
+                      int32_t* finished, float* feat, float* pol, int32_t* remaining, int sim_budget);
 void launch_status(const EngineView& E, int32_t* out, hipStream_t s);
 
 // adjudicate.hip: after the solver ran over the n pending positions (score,

@@ -451,6 +451,11 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
     m.def("get_flips", &oamd_host_flips, "move_mask"_a, "player_discs"_a, "opponent_discs"_a);
     m.def("device_count", &device_count);
     m.def("abi_version", &oamd_abi_version);
+    m.def("playout_cap_is_full",
+          [](uint64_t game_key, int ply, float full_probability) {
+              return oamd_playout_cap_is_full(game_key, ply, full_probability) != 0;
+          },
+          "game_key"_a, "ply"_a, "full_probability"_a);
     m.def("set_resnet_c128_four_wave", [](bool enable) { check(oamd_set_resnet_c128_four_wave(enable ? 1 : 0)); });
     m.def("resnet_c128_four_wave", []() { return oamd_resnet_c128_four_wave() != 0; });
     m.def("source_hash", [](const std::string& family) {
@@ -678,6 +683,23 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                  oamd_selfplay_config c{temperature_moves, temperature, opening_moves, emit ? 1 : 0};
                  check(oamd_engine_selfplay_steps_adjudicated(
                      e.h, reinterpret_cast<oamd_net*>(net), &c, n_moves, per_move_outputs ? 1 : 0,
+                     reinterpret_cast<int32_t*>(actions), reinterpret_cast<int32_t*>(finished),
+                     reinterpret_cast<float*>(feat), reinterpret_cast<float*>(pol), max_empties, split ? 1 : 0,
+                     reinterpret_cast<int32_t*>(margin)));
+             })
+        // playout cap randomization (fast_simulations 0 = off) and the work-budget call
+        .def("set_playout_cap",
+             [](Engine& e, float full_probability, int fast_simulations) {
+                 const oamd_playout_cap c{full_probability, fast_simulations};
+                 check(oamd_engine_set_playout_cap(e.h, fast_simulations == 0 ? nullptr : &c));
+             })
+        .def("selfplay_steps_budget",
+             [](Engine& e, uintptr_t net, int max_moves, int sim_budget, int temperature_moves, float temperature,
+                int opening_moves, bool emit, bool per_move_outputs, uintptr_t actions, uintptr_t finished,
+                uintptr_t feat, uintptr_t pol, int max_empties, bool split, uintptr_t margin) {
+                 oamd_selfplay_config c{temperature_moves, temperature, opening_moves, emit ? 1 : 0};
+                 check(oamd_engine_selfplay_steps_budget(
+                     e.h, reinterpret_cast<oamd_net*>(net), &c, max_moves, sim_budget, per_move_outputs ? 1 : 0,
                      reinterpret_cast<int32_t*>(actions), reinterpret_cast<int32_t*>(finished),
                      reinterpret_cast<float*>(feat), reinterpret_cast<float*>(pol), max_empties, split ? 1 : 0,
                      reinterpret_cast<int32_t*>(margin)));

@@ -40,7 +40,7 @@ constexpr int kCommitWaves = kCommitThreads / 64;
 constexpr int kGatherWaves = 4;
 
 // finished word of the self-play driver (tree.hip selfplay_move_game)
-constexpr int kFinOutcome = 3, kFinNoTargets = 4, kFinOverflow = 8, kFinSolverFlag = 64;
+constexpr int kFinOutcome = 3, kFinNoTargets = 4, kFinOverflow = 8, kFinSolverFlag = 64, kFinFast = 128;
 
 __device__ __forceinline__ void raise_flag(int64_t* counters, int bit) {
     // sticky OR: the result does not depend on the order of the updates
@@ -51,6 +51,9 @@ __device__ __forceinline__ void raise_flag(int64_t* counters, int bit) {
 // in an error row stages nothing, and if it also finished on this move its
 // staged moves are dropped (pending = -1, moves = 0). pending[g] = number of
 // staged moves to commit for a game that finished on this move, else -1.
+// A move that followed a fast search (playout cap, kFinFast) has no targets by
+// design: it stages nothing and raises no flag of its own, and the game's
+// other moves and its commit go on as ever.
 __global__ __launch_bounds__(64) void k_replay_add(oamd_replay_view V, const int32_t* actions,
                                                    const int32_t* finished, const float* feat, const float* pol) {
     const int g = blockIdx.x;
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(64) void k_replay_add(oamd_replay_view V, const int
     const int H2 = 2 * V.history_size;
     const int C = 1 + H2;
     const int fin = finished[g];
-    const bool played = actions[g] >= 0;
+    const bool played = actions[g] >= 0 && !(fin & kFinFast);
     int m = V.moves[g];
     int err = 0;
     if (fin & kFinOverflow) err |= OAMD_REPLAY_OVERFLOW;

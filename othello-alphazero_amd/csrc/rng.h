@@ -45,6 +45,14 @@ OAMD_HD int draw_transform(uint64_t game_key, uint64_t event) {
     return (int)(mix64(stream_key(game_key, event, 0)) >> 61);
 }
 
+// Playout cap randomization: whether the search of a game at
+// `ply` (moves since its last restart or opening) is a full one. A function
+// of the game's key and the ply alone: it consumes no event of the game's
+// stream, whose events count up from 0 and never reach bit 63.
+OAMD_HD bool playout_cap_full(uint64_t game_key, int32_t ply, float full_probability) {
+    return uniform(stream_key(game_key, (1ULL << 63) | (uint64_t)ply, 0), 0) < full_probability;
+}
+
 OAMD_HD float bits_to_float(uint32_t u) { return __builtin_bit_cast(float, u); }
 OAMD_HD uint32_t float_to_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 

@@ -288,7 +288,7 @@ __device__ __forceinline__ void select_range(const EngineView& E, int g, GameSta
                                              int hist_n, unsigned long long& sims,
                                              unsigned long long& evals, int* cnt, int list_base,
                                              unsigned long long& depth_sum, int& depth_max,
-                                             unsigned long long& scan_sum) {
+                                             unsigned long long& scan_sum, bool fast) {
     const int lane = lane_id();
     const int root = gs->root;
     const uint64_t key = gs->key;
@@ -344,7 +344,7 @@ __device__ __forceinline__ void select_range(const EngineView& E, int g, GameSta
                 const int total = wave_scan_first_n(lane < nc ? cs.n : 0, 0, [](int a, int b) { return a + b; }, nc);
                 const float mult = er * sqrt_count(E, total);
                 float prob = cs.p;
-                if (node == root && E.eps > 0.0f) {
+                if (node == root && !fast && E.eps > 0.0f) {  // a fast search draws no root noise
                     // fresh Dirichlet noise on every root selection (search_thread.cpp:230-249)
                     TS_T(tn0);
                     const int slots = 64 / nc;
@@ -714,7 +714,8 @@ __device__ __forceinline__ void backup_range(const EngineView& E, int g, size_t 
 // units of 2 on gfx950) so that a tree wave fits beside the two 208-VGPR
 // k_resnet_w8 waves of every SIMD (512 VGPRs): one pipeline group's tree round
 // runs on the CUs that the other group's ResNet launch occupies. The cap costs
-// 56 bytes per lane of spills (60 in k_tree_free); launches of at most
+// 60 bytes per lane of spills (72 in k_tree_free; DESIGN.md §17 has the
+// remarks of this tree and of the one before the playout cap); launches of at most
 // kWideTreeGames games run k_tree_wide, the same round uncapped (114 VGPRs).
 // Evaluation list (cnt_add != nullptr, the native search): the rows of
 // non-terminal leaves this round selects are appended to E.rowlist[g0 * L ..]
@@ -738,18 +739,32 @@ struct RoundAcc {
     unsigned expansions = 0;          // leaves expanded (children = the node count's growth)
 };
 
+// Playout cap randomization: the batches per virtual thread
+// and the root noise weight of the search of game gs at its current root.
+// Off (E.fast_steps == 0): the engine's. On: a search that playout_cap_full
+// calls fast runs E.fast_steps batches and draws no root noise. Both are
+// wave-uniform (one readfirstlane of the draw), recomputed every round from
+// the game's key and ply, which do not change during a search.
+__device__ __forceinline__ bool search_is_fast(const EngineView& E, const GameState* gs) {
+    if (E.fast_steps <= 0) return false;
+    const bool full = playout_cap_full(gs->key, gs->ply, E.full_probability);
+    return __builtin_amdgcn_readfirstlane(full ? 0 : 1) != 0;
+}
+__device__ __forceinline__ int search_steps_of(const EngineView& E, bool fast) { return fast ? E.fast_steps : E.steps; }
+
 // One round of game g's search schedule (see k_tree): virtual threads
 // [t0, t1) visited cyclically from rp, each backing up its pending batch and
 // selecting its next ones (chain splitting after `budget` re-selections, at
 // most `max_cuts` cuts per search; cut_at = the thread whose chain stopped).
 // Returns true when the search is complete after this round: every thread
 // selected its `steps` batches and none waits for the NN (the reference's
-// search has returned, mcts.h:252-255).
+// search has returned, mcts.h:252-255). fast: search_is_fast of this search
+// (its batches per thread are search_steps_of, and it draws no root noise).
 __device__ __forceinline__ bool search_round(const EngineView& E, int g, GameState* gs, size_t base, int t0,
                                              int t1, int B, bool do_backup, bool do_select, bool fresh, int rp,
                                              int budget, int max_cuts, int& cuts, bool& over, int& cut_at,
                                              uint64_t& event, int hist_node, int hist_n, int& count,
-                                             bool& overflow, int* cnt_add, int list_base, RoundAcc& acc) {
+                                             bool& overflow, int* cnt_add, int list_base, RoundAcc& acc, bool fast) {
     const int lane = lane_id();
     const int nt = t1 - t0;
     int chain = 0;  // re-selections after all-terminal batches in this round
@@ -775,7 +790,7 @@ __device__ __forceinline__ bool search_round(const EngineView& E, int g, GameSta
         // round trip (search_thread.cpp:102) and is backed up at once (:116-127),
         // then the thread selects again, up to `steps` batches per search
         bool again = false;  // the last batch was all terminal and is backed up
-        while (do_select && !pend && sel < E.steps) {
+        while (do_select && !pend && sel < search_steps_of(E, fast)) {
             if (again && budget > 0 && chain >= budget) {
                 if (cuts < max_cuts) {
                     cut_at = t;  // the next round continues this chain
@@ -787,7 +802,7 @@ __device__ __forceinline__ bool search_round(const EngineView& E, int g, GameSta
             const unsigned long long ev0 = acc.evals;
             TS_T(tsel0);
             select_range(E, g, gs, base, t * B, (t + 1) * B, event, hist_node, hist_n, acc.sims, acc.evals, cnt_add,
-                         list_base, acc.depth_sum, acc.depth_max, acc.scan_sum);
+                         list_base, acc.depth_sum, acc.depth_max, acc.scan_sum, fast);
             TS_T(tsel1);
             TS_ADD(kTsSelect, tsel1 - tsel0);
             TS_ADD(kTsBatches, 1);
@@ -807,7 +822,7 @@ __device__ __forceinline__ bool search_round(const EngineView& E, int g, GameSta
             }
         }
         if (lane == 0) *ts = sel | (pend ? kTstatePend : 0);
-        done = done && sel >= E.steps && !pend;
+        done = done && sel >= search_steps_of(E, fast) && !pend;
     }
     return done && cut_at < 0;
 }
@@ -886,6 +901,9 @@ __device__ __forceinline__ void tree_round_kernel(const EngineView& E, int g0, i
         }
         return;
     }
+    // a game on a fast search stops selecting after its own steps and idles
+    // for the launch's remaining rounds
+    const bool fast = search_is_fast(E, gs);
     uint64_t event = gs->event;
     const int hist_n = gs->hist_n;
     const int hist_node = lane < 16 ? gs->hist[lane] : -1;
@@ -898,7 +916,7 @@ __device__ __forceinline__ void tree_round_kernel(const EngineView& E, int g0, i
     bool over = false;  // a chain went past the budget with every cut used
     int cut_at = -1;    // the thread whose chain this round stopped
     search_round(E, g, gs, base, t0, t1, B, do_backup != 0, do_select != 0, fresh != 0, rp, budget, max_cuts, cuts,
-                 over, cut_at, event, hist_node, hist_n, count, overflow, cnt_add, g0 * E.L, acc);
+                 over, cut_at, event, hist_node, hist_n, count, overflow, cnt_add, g0 * E.L, acc, fast);
     if (lane == 0) {
         if (budget > 0) {
             gs->resume = cut_at >= 0 ? cut_at : rp;
@@ -1284,10 +1302,12 @@ __device__ __forceinline__ void store_pending(oamd_position* slot, int player, c
 }
 
 // One self-play move of game g (one wave): outputs at index g of the given
-// per-move slices.
+// per-move slices. fast: the root's search was a fast one (search_is_fast at
+// the ply of the searched root, before the move): the move is chosen and
+// applied as ever, but writes no targets and reports kFinFast.
 __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const SelfplayParams& sp, int g,
                                                    int32_t* actions, int32_t* finished, float* feat_out,
-                                                   float* pol_out, oamd_position* pending) {
+                                                   float* pol_out, oamd_position* pending, bool fast) {
     const int lane = lane_id();
     GameState* gs = E.games + g;
     const size_t base = (size_t)g * E.cap;
@@ -1304,7 +1324,7 @@ __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const Se
     if (lk.player != 0) {
         const uint64_t ev = gs->event;
         action = choose_root_action(E, gs, base, lk, rp, sp.temperature_moves, sp.temperature);
-        if (sp.emit_targets && feat_out && nc > 0) {
+        if (sp.emit_targets && feat_out && nc > 0 && !fast) {
             const int C = 1 + 2 * E.H;
             for (int t = 0; t < 8; ++t)
                 write_targets(E, g, t, feat_out + (size_t)g * 8 * C * 64, pol_out + (size_t)g * 8 * 65);
@@ -1343,7 +1363,7 @@ __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const Se
             random_opening(E, g, sp.opening_moves);
         }
         if (actions) actions[g] = action;
-        if (finished) finished[g] = fin | status;
+        if (finished) finished[g] = fin | status | (fast && action >= 0 ? kFinFast : 0);
     }
 }
 
@@ -1360,7 +1380,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(EngineView E, SelfplayPara
         }
         return;
     }
-    selfplay_move_game(E, sp, g, actions, finished, feat_out, pol_out, sp.adj_pending);
+    selfplay_move_game(E, sp, g, actions, finished, feat_out, pol_out, sp.adj_pending, search_is_fast(E, gs));
 }
 
 // Per-game search mask (oamd_engine_set_active): k_tree, k_selfplay_move and
@@ -1526,17 +1546,27 @@ __global__ __launch_bounds__(64) void k_arena_move(EngineView EA, EngineView EB,
 // launches stay full and no extra rounds are needed. The host enqueues rounds
 // until `remaining` (games of the group with moves left) reads 0.
 // ---------------------------------------------------------------------------
+//
+// Work budget (sim_budget > 0, per-move outputs only): n_moves
+// is the number of output slices and the most moves a game plays; a game
+// stops after the move whose search brought the nominal simulations (steps x
+// L) of the searches it started in this call to sim_budget or more, so it
+// overshoots by less than one search. Every slice of every game is pre-filled
+// with action -1 / finished 0 ("nothing played"), and the played moves
+// overwrite a prefix of them.
 __global__ void k_free_begin(EngineView E, int g0, int ng, int n_moves, int32_t* remaining, int32_t* actions,
-                             int32_t* finished, int per_move) {
+                             int32_t* finished, int per_move, int sim_budget) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;  // *remaining zeroed by the caller
     if (i >= ng) return;
     const int g = g0 + i;
     GameState* gs = E.games + g;
     const bool active = (gs->flags & kActive) != 0 && n_moves > 0;
     gs->moves_left = active ? n_moves : 0;
+    gs->sims_left = active ? sim_budget : 0;
     gs->fresh = 1;
     if (active) atomicAdd(remaining, 1);
-    for (int m = 0; !active && m < (per_move ? n_moves : (n_moves > 0 ? 1 : 0)); ++m) {
+    const bool fill = !active || sim_budget > 0;
+    for (int m = 0; fill && m < (per_move ? n_moves : (n_moves > 0 ? 1 : 0)); ++m) {
         if (actions) actions[(size_t)m * E.G + g] = -1;
         if (finished) finished[(size_t)m * E.G + g] = 0;
     }
@@ -1544,7 +1574,8 @@ __global__ void k_free_begin(EngineView E, int g0, int ng, int n_moves, int32_t*
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_tree_free(
     EngineView E, int g0, int B, int* cnt_add, int* cnt_reset, int budget, int timed, SelfplayParams sp, int n_moves,
-    int per_move, int32_t* actions, int32_t* finished, float* feat_out, float* pol_out, int32_t* remaining) {
+    int per_move, int32_t* actions, int32_t* finished, float* feat_out, float* pol_out, int32_t* remaining,
+    int sim_budget) {
     const int g = g0 + (int)blockIdx.x;
     const int lane = lane_id();
     if (cnt_reset && blockIdx.x == 0 && lane == 0) *cnt_reset = 0;
@@ -1569,8 +1600,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_tre
     int cut_at = -1;
     // no extra rounds to budget for: a game may cut its chains any number of times
     constexpr int kNoCap = 0x3FFFFFFF;
+    const bool fast = search_is_fast(E, gs);  // this round's search (the ply of its root)
     const bool done = search_round(E, g, gs, base, 0, T, B, true, true, fresh, rp, budget, kNoCap, cuts, over, cut_at,
-                                   event, hist_node, hist_n, count, overflow, cnt_add, g0 * E.L, acc);
+                                   event, hist_node, hist_n, count, overflow, cnt_add, g0 * E.L, acc, fast);
     if (done) {
         // the search has returned: publish the wave's state, then the move
         // (k_selfplay_move's), which reads it from memory
@@ -1587,8 +1619,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_tre
         const size_t C = 1 + 2 * (size_t)E.H;
         selfplay_move_game(E, sp, g, actions ? actions + slot : nullptr, finished ? finished + slot : nullptr,
                            feat_out ? feat_out + slot * 8 * C * 64 : nullptr, pol_out ? pol_out + slot * 8 * 65 : nullptr,
-                           sp.adj_pending ? sp.adj_pending + slot : nullptr);
+                           sp.adj_pending ? sp.adj_pending + slot : nullptr, fast);
         --moves;
+        if (sim_budget > 0) {
+            // work budget: the search just played is charged its nominal size;
+            // the move that uses the budget up is the game's last of the call
+            const int left = __builtin_amdgcn_readfirstlane(gs->sims_left) - search_steps_of(E, fast) * E.L;
+            if (lane == 0) gs->sims_left = left;
+            if (left <= 0) moves = 0;
+        }
         __builtin_amdgcn_wave_barrier();
         wait_stores();  // (a compiler barrier too: the reloads below see the move's stores)
         event = gs->event;
@@ -1599,9 +1638,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_tre
         rp = 0;
         cuts = 0;
         cut_at = -1;
-        if (moves > 0)  // the next search's first round, in this same round
+        if (moves > 0) {  // the next search's first round, in this same round
+            const bool fast2 = search_is_fast(E, gs);  // the new root's ply (and key, after a restart)
             search_round(E, g, gs, base, 0, T, B, true, true, true, 0, budget, kNoCap, cuts, over, cut_at, event,
-                         hist_node, hist_n, count, overflow, cnt_add, g0 * E.L, acc);
+                         hist_node, hist_n, count, overflow, cnt_add, g0 * E.L, acc, fast2);
+        }
     }
     if (lane == 0) {
         gs->moves_left = moves;
@@ -1713,17 +1754,17 @@ void launch_arena_move(const EngineView& EA, const EngineView& EB, const Selfpla
     hipLaunchKernelGGL(k_arena_move, dim3(EA.G), dim3(64), 0, s, EA, EB, sp, actions, finished, discs, remaining);
 }
 void launch_free_begin(const EngineView& E, int g0, int ng, int n_moves, int32_t* remaining, int32_t* actions,
-                       int32_t* finished, int per_move, hipStream_t s) {
+                       int32_t* finished, int per_move, int sim_budget, hipStream_t s) {
     if (ng > 0)
         hipLaunchKernelGGL(k_free_begin, dim3(blocks_for(ng, 256)), dim3(256), 0, s, E, g0, ng, n_moves, remaining,
-                           actions, finished, per_move);
+                           actions, finished, per_move, sim_budget);
 }
 void launch_tree_free(const EngineView& E, hipStream_t s, int g0, int ng, int B, int* cnt_add, int* cnt_reset,
                       int budget, bool timed, const SelfplayParams& sp, int n_moves, int per_move, int32_t* actions,
-                      int32_t* finished, float* feat, float* pol, int32_t* remaining) {
+                      int32_t* finished, float* feat, float* pol, int32_t* remaining, int sim_budget) {
     if (ng > 0 && B > 0 && E.L % B == 0)
         hipLaunchKernelGGL(k_tree_free, dim3(ng), dim3(64), 0, s, E, g0, B, cnt_add, cnt_reset, budget, (int)timed, sp,
-                           n_moves, per_move, actions, finished, feat, pol, remaining);
+                           n_moves, per_move, actions, finished, feat, pol, remaining, sim_budget);
 }
 void launch_status(const EngineView& E, int32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(k_status, dim3(blocks_for(E.G, 64)), dim3(64), 0, s, E, out);

@@ -18,7 +18,10 @@ and host) and measure a move against perfect play;
 ``ReplayBuffer(track_exact=True).relabel_endgames`` uses the same solver to
 give the buffer's last plies exact value targets, and ``adjudicate_empties=K``
 (self-play, arena; ``adjudicate`` is the rule on the host) ends running games
-at K empties with the exact result.
+at K empties with the exact result. ``BatchedMCTS.set_playout_cap`` switches on
+playout cap randomization (full searches recorded, fast ones only played:
+``FIN_FAST``, ``playout_cap_is_full``), and ``selfplay_steps(sim_budget=...)``
+gives every game of a free-running call a work budget instead of a move count.
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -36,11 +39,12 @@ from ._othello_mcts_impl import (  # noqa: F401
     device_count,
     get_flips,
     get_legal_moves,
+    playout_cap_is_full,
 )
 from .batched import BatchedMCTS  # noqa: E402,F401
 from .arena import Arena, ArenaResult, paired_openings  # noqa: E402,F401
 from .native import NativeNet, load_checkpoint  # noqa: E402,F401
-from .selfplay import SelfPlayCollector, self_play  # noqa: E402,F401
+from .selfplay import FIN_FAST, SelfPlayCollector, self_play  # noqa: E402,F401
 from .replay import ReplayBuffer  # noqa: E402,F401
 from .endgame import EndgameSolution, endgame_move_loss, solve_endgames, solve_position  # noqa: E402,F401
 from .adjudication import adjudicate  # noqa: E402,F401
@@ -77,4 +81,6 @@ __all__ = [
     "solve_position",
     "endgame_move_loss",
     "adjudicate",
+    "FIN_FAST",
+    "playout_cap_is_full",
 ]

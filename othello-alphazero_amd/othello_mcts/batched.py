@@ -134,6 +134,29 @@ class BatchedMCTS:
             raise ValueError(f"Expected {self.num_games} mask entries, but got shape {tuple(m.shape)}.")
         self.engine.set_active(m.data_ptr())
 
+    def set_playout_cap(self, full_probability: float | None = None, fast_simulations: int | None = None) -> None:
+        """Playout cap randomization (KataGo, Wu 2019, section 3.1).
+        With a cap set, a game's search at a given ply is a full one
+        (num_simulations, root noise, its move recorded) with probability
+        ``full_probability``; otherwise a fast one: ``fast_simulations``, no
+        root noise, and the move that follows it is played but writes no targets
+        and carries FIN_FAST in ``finished``. Which one is a function of the
+        game's key and ply alone (``othello_mcts.playout_cap_is_full``), so no
+        other random draw of the game moves. ``None`` (both): off, the default.
+        The arena does not use the setting and rejects an engine that has it."""
+        if full_probability is None and fast_simulations is None:
+            self.engine.set_playout_cap(1.0, 0)
+            return
+        if full_probability is None or fast_simulations is None:
+            raise ValueError("Expected full_probability and fast_simulations together (or neither: off).")
+        p, n = float(full_probability), int(fast_simulations)
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"Expected 0 < full_probability <= 1, but got {full_probability}.")
+        if not 1 <= n <= self.config.num_simulations:
+            raise ValueError(f"Expected 1 <= fast_simulations <= num_simulations ({self.config.num_simulations}), "
+                             f"but got {fast_simulations}.")
+        self.engine.set_playout_cap(p, n)
+
     def random_openings(self, max_moves: int = 8, seed: int = 0) -> None:
         self._stream()
         self.engine.random_openings(max_moves, seed)
@@ -221,7 +244,7 @@ class BatchedMCTS:
     def selfplay_steps(self, neural_net, n_moves: int, temperature_moves: int = 12, temperature: float = 1.0,
                        opening_moves: int = 0, emit_targets: bool = False,
                        keep_all: bool = True, adjudicate_empties: int = 0,
-                       split: bool = False) -> dict[str, torch.Tensor]:
+                       split: bool = False, sim_budget: int = 0) -> dict[str, torch.Tensor]:
         """n_moves x (search(net) + selfplay_move(...)) in one enqueue, same results
         move for move; each pipeline group chains its searches and moves on its own
         stream, so the per-move join disappears (oamd_engine_selfplay_steps).
@@ -229,8 +252,23 @@ class BatchedMCTS:
         (G, ...), every move writing the same buffers. Native net (or a module
         search() would convert) only. adjudicate_empties / split: as
         selfplay_move, ``out["margin"]`` shaped like ``finished``; with more than
-        one move it needs keep_all=True (ValueError otherwise)."""
+        one move it needs keep_all=True (ValueError otherwise).
+
+        sim_budget = S > 0 (free-running games only, keep_all=True): a work
+        budget per game in place of the move count. n_moves is then the number
+        of output slices and the most moves a game plays; a game stops after the
+        move whose search brought the nominal simulations of the searches it
+        started in this call to S or more (it overshoots by less than one
+        search). A game's moves fill a prefix of its slices, and the slices it
+        did not reach hold action -1 and finished 0. Meant for a playout cap
+        (set_playout_cap), where games given the same number of moves would
+        finish the call at very different times."""
         k = check_adjudicate_empties(adjudicate_empties, max(0, int(n_moves)), keep_all)
+        sim_budget = int(sim_budget)
+        if sim_budget < 0:
+            raise ValueError(f"Expected sim_budget >= 0, but got {sim_budget}.")
+        if sim_budget > 0 and not keep_all:
+            raise ValueError("sim_budget needs keep_all=True: games play different numbers of moves in the call.")
         self._stream()
         net = resolve(neural_net, self.device.index, self.config.history_size)
         if net is None:
@@ -246,12 +284,14 @@ class BatchedMCTS:
         fp = feat.data_ptr() if feat is not None else 0
         pp = pol.data_ptr() if pol is not None else 0
         out = {"actions": actions, "finished": finished}
-        if k > 0:
-            margin = torch.empty_like(actions)
-            self.engine.selfplay_steps_adjudicated(net.handle, n, temperature_moves, temperature, opening_moves,
-                                                   emit_targets, keep_all, actions.data_ptr(), finished.data_ptr(),
-                                                   fp, pp, k, bool(split), margin.data_ptr())
-            out["margin"] = margin
+        if k > 0 or sim_budget > 0:
+            margin = torch.empty_like(actions) if k > 0 else None
+            self.engine.selfplay_steps_budget(net.handle, n, sim_budget, temperature_moves, temperature,
+                                              opening_moves, emit_targets, keep_all, actions.data_ptr(),
+                                              finished.data_ptr(), fp, pp, k, bool(split),
+                                              margin.data_ptr() if k > 0 else 0)
+            if k > 0:
+                out["margin"] = margin
         else:
             self.engine.selfplay_steps(net.handle, n, temperature_moves, temperature, opening_moves, emit_targets,
                                        keep_all, actions.data_ptr(), finished.data_ptr(), fp, pp)

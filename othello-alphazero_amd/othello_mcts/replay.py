@@ -86,6 +86,9 @@ class ReplayBuffer:
     (``SampleBuffer``'s rule) and move into the ring in ascending game order,
     the oldest positions overwritten. Rows the kernels refuse set sticky flags;
     ``check()`` raises them with ``SampleBuffer``'s messages.
+    A move played after a fast search of a playout cap (``FIN_FAST`` in
+    ``finished``, ``BatchedMCTS.set_playout_cap``) carries no targets: it is
+    skipped, without a flag, and the game's outcome labels its other moves.
 
     ``track_exact=True``: the ring also keeps ``exact`` (``capacity`` int8:
     ``EXACT_UNKNOWN``, ``EXACT_GAVE_UP`` or the exact disc difference for the

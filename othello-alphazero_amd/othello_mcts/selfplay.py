@@ -32,6 +32,9 @@ FIN_NO_TARGETS, FIN_OVERFLOW = 4, 8
 # game was ended at this move by the exact solver (bits 0-1 carry its exact
 # outcome), bit 6 the solver flagged the position (an error)
 FIN_ADJUDICATED, FIN_SOLVER_FLAG = 32, 64
+# with a playout cap (BatchedMCTS.set_playout_cap): bit 7 the move
+# followed a fast search: it was played, but no targets were written for it
+FIN_FAST = 128
 _OUTCOME_BLACK = {FIN_DRAW: 0.0, FIN_BLACK: 1.0, FIN_WHITE: -1.0}
 
 
@@ -82,12 +85,15 @@ class SelfPlayCollector:
         if bool(flagged.any()):
             raise RuntimeError(f"the exact solver flagged the adjudicated position of game(s) "
                                f"{flagged.nonzero().flatten().tolist()}")
+        # a move after a fast search (playout cap) is played but not recorded;
+        # the game's outcome still labels its recorded moves
+        fast = (finished & FIN_FAST) != 0
         no_targets = (finished & FIN_NO_TARGETS) != 0
-        if bool((no_targets & (actions >= 0)).any()):
+        if bool((no_targets & (actions >= 0) & ~fast).any()):
             # the reference's self_play_data raises here (mcts.cpp:69-71)
             raise ValueError("The root node has not been expanded yet.")
         for g in range(self.num_games):
-            if int(actions[g]) >= 0:  # a searched, expanded root: targets were written
+            if int(actions[g]) >= 0 and not bool(fast[g]):  # a searched, expanded root: targets were written
                 self._moves[g].append((feats[g], pols[g]))
             fin = int(finished[g]) & 3
             if fin != FIN_NONE:
@@ -118,7 +124,8 @@ class SelfPlayCollector:
 def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temperature: float = 1.0,
               opening_moves: int = 0, device: str | torch.device = "cpu",
               moves_per_call: int = 16, adjudicate_empties: int = 0,
-              split: bool = False) -> dict[str, list[torch.Tensor]]:
+              split: bool = False, playout_cap: tuple[float, int] | None = None,
+              sim_budget: int = 0) -> dict[str, list[torch.Tensor]]:
     """Play until at least ``games`` games have completed across the batch (each
     slot restarts when its game ends) and return their samples in the
     reference's ``_self_play`` format (train.py:404-452). ``opening_moves=0``
@@ -138,22 +145,37 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
     at most K empties, with the exact result of that position as its outcome
     (othello_mcts.adjudication; ``split``: the split solver). The samples then
     hold no position with K or fewer empties except the first searched move
-    after a restart whose opening already went that far."""
+    after a restart whose opening already went that far.
+
+    playout_cap = (full_probability, fast_simulations): sets the engine's
+    playout cap for this run (``BatchedMCTS.set_playout_cap``; None leaves the
+    engine as it is). Moves after fast searches are played but yield no
+    samples. sim_budget = S > 0 (native net, moves_per_call > 1): every call
+    gives each game S nominal simulations instead of ``moves_per_call`` moves
+    (``BatchedMCTS.selfplay_steps``); ``moves_per_call`` is then the slot count,
+    the most moves of a game per call."""
     from .adjudication import check_adjudicate_empties
     from .native import resolve
 
     check_adjudicate_empties(adjudicate_empties)
+    if playout_cap is not None:
+        batched.set_playout_cap(*playout_cap)
+    sim_budget = int(sim_budget)
+    if sim_budget < 0:
+        raise ValueError(f"Expected sim_budget >= 0, but got {sim_budget}.")
 
     col = SelfPlayCollector(batched.num_games, device=device)
     data = {"features": [], "policies": [], "values": []}
     native = moves_per_call > 1 and resolve(neural_net, batched.device.index, batched.config.history_size) is not None
+    if sim_budget > 0 and not native:
+        raise ValueError("sim_budget needs a native net and moves_per_call > 1 (the free-running call).")
     kw = dict(temperature_moves=temperature_moves, temperature=temperature, opening_moves=opening_moves,
               emit_targets=True)
     if adjudicate_empties:
         kw.update(adjudicate_empties=adjudicate_empties, split=split)
     while col.games_completed < games:
         if native:
-            out = batched.selfplay_steps(neural_net, moves_per_call, keep_all=True, **kw)
+            out = batched.selfplay_steps(neural_net, moves_per_call, keep_all=True, sim_budget=sim_budget, **kw)
             moves = [{k: v[i] for k, v in out.items()} for i in range(moves_per_call)]
         else:
             batched.search(neural_net)
@@ -167,4 +189,4 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
 
 __all__ = ["SelfPlayCollector", "self_play", "outcome_for_black", "value_targets_from_outcome",
            "FIN_NO_TARGETS", "FIN_OVERFLOW", "FIN_NONE", "FIN_DRAW", "FIN_BLACK", "FIN_WHITE", "FIN_ADJUDICATED",
-           "FIN_SOLVER_FLAG"]
+           "FIN_SOLVER_FLAG", "FIN_FAST"]

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import torch
 
-from .selfplay import FIN_NO_TARGETS, FIN_OVERFLOW, FIN_NONE
+from .selfplay import FIN_FAST, FIN_NO_TARGETS, FIN_OVERFLOW, FIN_NONE
 
 _OUTCOME = torch.tensor([0.0, 0.0, 1.0, -1.0])  # finished code (bits 0-1) -> outcome for black
 
@@ -76,7 +76,8 @@ class SampleBuffer:
         if bool(((fin & FIN_OVERFLOW) != 0).any()):
             raise RuntimeError("node pool exhausted: the search no longer matches the reference; "
                                "use a larger node_capacity")
-        played = actions >= 0
+        # (a move after a fast search, playout cap: played but not recorded)
+        played = (actions >= 0) & ((fin & FIN_FAST) == 0)
         if bool(((fin & FIN_NO_TARGETS) != 0)[played].any()):
             raise ValueError("The root node has not been expanded yet.")
         g = torch.nonzero(played).flatten()

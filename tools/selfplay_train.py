@@ -13,7 +13,7 @@ descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
 Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds]
-                 [packed [exact=K]] [adjudicate=K] [split]
+                 [packed [exact=K]] [adjudicate=K] [split] [cap=P:N] [budget=S]
 
 packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
 million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
@@ -34,6 +34,13 @@ gains adjudicated (games the solver ended in the iteration), resolve_ms (device
 events around the resolve step, mean over the iteration's selfplay_steps
 calls; reading them waits for each call, a host wait the K = 0 run does not
 have) and resolve_share (their sum over the self-play phase).
+
+cap=P:N: playout cap randomization (BatchedMCTS.set_playout_cap(P, N), DESIGN.md
+§17): a search is a full one (800 simulations, recorded) with probability P,
+else N simulations, played but not recorded. budget=S: every selfplay_steps
+call gives each game S nominal simulations instead of 16 moves
+(selfplay_steps(sim_budget=S)); the call's slot count is the most moves S buys
+(S / N rounded up with a cap, S / 800 without), 64 at the most.
 
 new_positions (packed) is the ring head's advance, valid while one iteration
 stores fewer positions than the ring holds; new_games / selfplay_s and
@@ -111,6 +118,13 @@ def main():
     split = "split" in sys.argv[5:]
     if split and not (exact or K):
         raise SystemExit("split needs exact=K or adjudicate=K")
+    cap = [w[4:].split(":") for w in sys.argv[5:] if w.startswith("cap=")]
+    cap = (float(cap[0][0]), int(cap[0][1])) if cap else None
+    budget = [int(w[7:]) for w in sys.argv[5:] if w.startswith("budget=")]
+    budget = budget[0] if budget else 0
+    L = 2 * 16
+    nominal_min = -(-(cap[1] if cap else 800) // L) * L  # the smallest search's nominal simulations
+    slots = min(64, -(-budget // nominal_min)) if budget else 16
     moves_per_iter = 64
     torch.manual_seed(0)
     dev = torch.device("cuda", 0)
@@ -122,6 +136,8 @@ def main():
     b = om.BatchedMCTS(G, history_size=8, num_simulations=800, num_threads=2, batch_size=16,
                        dirichlet_epsilon=0.25, dirichlet_alpha=0.5, seed=77)
     b.reset()
+    if cap:
+        b.set_playout_cap(*cap)
     if packed:
         buf = om.ReplayBuffer(G, 8, capacity=500_000, device=dev, track_exact=bool(exact))
     else:
@@ -137,8 +153,8 @@ def main():
         if K and it == 0:
             b.engine.adjudicate_ms()  # switches the resolve step's events on
         for _ in range(moves_per_iter // 16):  # 16 moves per call: bounded output buffers
-            o = b.selfplay_steps(native, 16, temperature_moves=12, opening_moves=0, emit_targets=True,
-                                 keep_all=True, adjudicate_empties=K, split=split and K > 0)
+            o = b.selfplay_steps(native, slots, temperature_moves=12, opening_moves=0, emit_targets=True,
+                                 keep_all=True, adjudicate_empties=K, split=split and K > 0, sim_budget=budget)
             if K:
                 n_adj = ((o["finished"] & 32) != 0).sum()  # stays on the device until the phase is over
                 adjudicated = n_adj if adjudicated is None else adjudicated + n_adj
@@ -147,7 +163,7 @@ def main():
             if packed:
                 buf.add(o)
             else:
-                for i in range(16):
+                for i in range(slots):
                     buf.add({k: v[i] for k, v in o.items()})
         torch.cuda.synchronize()
         t1 = time.time()
@@ -192,7 +208,8 @@ def main():
                                                     "buffer": "packed" if packed else "fp32",
                                                     "exact_max_empties": exact[0] if exact else None,
                                                     "exact_split": split and bool(exact),
-                                                    "adjudicate_empties": K, "adjudicate_split": split and K > 0},
+                                                    "adjudicate_empties": K, "adjudicate_split": split and K > 0,
+                                                    "playout_cap": cap, "sim_budget": budget, "slots_per_call": slots},
                                                    indent=1))
 
 
