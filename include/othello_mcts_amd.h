@@ -359,10 +359,63 @@ int oamd_engine_selfplay_steps_budget(oamd_engine *e, oamd_net *net, const oamd_
                                       int32_t *actions_dev, int32_t *finished_dev, float *features_dev,
                                       float *policy_dev, int32_t max_empties, int32_t split,
                                       int32_t *margin_dev);
+
+/* Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2;
+ * DESIGN.md §18; opt-in, off by default). All arithmetic below is fp32 in the
+ * order written.
+ *
+ * Forced playouts: at the root of a FULL search (every search without a
+ * playout cap; never a fast one), a selection with more than one child scores
+ * child c with n_c visits (in-flight ones included) as
+ *     forced_c = n_c > 0 && (float)n_c * (float)n_c < (k * prob_c) * (float)total
+ *     ucb_c    = forced_c ? +inf : q_c + mult * prob_c / (1 + (float)n_c)
+ * where prob_c is the prior of this selection's PUCT line (the noised one when
+ * dirichlet_epsilon > 0) and total the children's visit sum: a child that has
+ * been tried keeps a floor of sqrt(k * prob_c * total) visits. The first
+ * maximum wins, so the forced child of the lowest index is taken. The rule
+ * consumes no random event and does not depend on dirichlet_epsilon.
+ *
+ * Policy target pruning (prune_targets != 0): the self-play targets
+ * (oamd_engine_self_play_data, oamd_engine_selfplay_move / _steps) are written
+ * from the pruned counts of oamd_prune_visit_counts in place of the raw visit
+ * counts, n'_j / sum n'. Visit counts and Q as queried, the move choice, every
+ * `finished` bit and tree reuse do not change.
+ *
+ * The arena does not use the setting and rejects an engine that has it. */
+typedef struct oamd_forced_playouts {
+    float k;               /* finite, > 0; KataGo uses 2 */
+    int32_t prune_targets; /* 1: targets from the pruned counts */
+} oamd_forced_playouts;
+/* fp = NULL: off. OAMD_INVALID_ARGUMENT unless k is finite and > 0. */
+int oamd_engine_set_forced_playouts(oamd_engine *e, const oamd_forced_playouts *fp);
+/* The pruning rule (host; the code the device runs). visits, q and priors (the
+ * stored priors, without noise) are the root's n_children children in child
+ * order, root_visit_count the root's own N. With n_children <= 1 or
+ * total = sum visits = 0 the counts are copied. Else best = the first child
+ * with the most visits, mult = explore_rate(root_visit_count) *
+ * sqrtf((float)total) with explore_rate(N) = logf(((float)(1 + N) + c_puct_base)
+ * / c_puct_base) + c_puct_init, u(j, m) = q_j + mult * p_j / (1.0f + (float)m),
+ * ubest = u(best, n_best), and for every j != best with n_j > 0:
+ *     cap = (int)sqrtf((k * p_j) * (float)total);  m = n_j
+ *     at most cap times, while m > 0: if u(j, m - 1) < ubest then m -= 1 else stop
+ *     if m < n_j and m == 1 then m = 0
+ *     pruned_out[j] = m
+ * pruned_out[best] = n_best. OAMD_INVALID_ARGUMENT: n_children outside 0..64,
+ * a negative count, k not finite or <= 0. */
+int oamd_prune_visit_counts(int32_t n_children, int32_t root_visit_count, const int32_t *visits,
+                            const float *q, const float *priors, float c_puct_base, float c_puct_init,
+                            float k, int32_t *pruned_out);
+/* The stored priors P of every game's root children: priors_dev (G, 65) by
+ * action like oamd_engine_root_stats, 0 where there is no child. Enqueued
+ * only. */
+int oamd_engine_root_priors(oamd_engine *e, float *priors_dev);
 /* Reset every game to a random opening. */
 int oamd_engine_random_openings(oamd_engine *e, int32_t max_moves, uint64_t seed);
 /* The random-stream key of a game (DESIGN.md "Random streams"). */
 int oamd_engine_game_key(oamd_engine *e, int32_t game, uint64_t *key_host);
+/* The number of events the game has drawn from its stream since its last
+ * reset or restart: the index of its next draw (waits for the engine's stream). */
+int oamd_engine_game_event(oamd_engine *e, int32_t game, uint64_t *event_host);
 
 /* Per-game search mask: active_dev (G) bytes, nonzero = the game is searched,
  * moved by oamd_engine_selfplay_move and by oamd_engine_apply_actions; NULL =

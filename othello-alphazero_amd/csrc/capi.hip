@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "capi_internal.h"
+#include "forced.h"
 #include "rng.h"
 
 using namespace oamd;
@@ -775,6 +776,14 @@ int oamd_engine_root_stats(oamd_engine* e, int32_t* visits_dev, float* q_dev, oa
     return OAMD_OK;
 }
 
+int oamd_engine_root_priors(oamd_engine* e, float* priors_dev) {
+    if (!priors_dev) return fail(OAMD_INVALID_ARGUMENT, "priors_dev is null");
+    DeviceGuard dg(e->device);
+    launch_root_priors(e->view(), priors_dev, e->stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
 int oamd_engine_self_play_data(oamd_engine* e, int32_t game, float* features, float* policy) {
     oamd_root_info info;
     int rc = oamd_engine_root_info(e, game, &info, nullptr, nullptr);
@@ -982,6 +991,50 @@ int oamd_playout_cap_is_full(uint64_t game_key, int32_t ply, float full_probabil
     return playout_cap_full(game_key, ply, full_probability) ? 1 : 0;
 }
 
+int oamd_engine_set_forced_playouts(oamd_engine* e, const oamd_forced_playouts* fp) {
+    if (!fp) {
+        e->forced_k = 0.0f;
+        e->prune_targets = false;
+        e->end_search();
+        return OAMD_OK;
+    }
+    if (!(std::isfinite(fp->k) && fp->k > 0.0f))
+        return fail(OAMD_INVALID_ARGUMENT, "Expected a finite forced playout factor k > 0, but got " + std::to_string(fp->k) + ".");
+    e->forced_k = fp->k;
+    e->prune_targets = fp->prune_targets != 0;
+    e->end_search();
+    return OAMD_OK;
+}
+
+// The rule of tree.hip root_target_count on the host: the same forced.h code,
+// the exploration rate as build_tables computes it.
+int oamd_prune_visit_counts(int32_t n_children, int32_t root_visit_count, const int32_t* visits, const float* q,
+                            const float* priors, float c_puct_base, float c_puct_init, float k, int32_t* pruned_out) {
+    if (n_children < 0 || n_children > 64)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= n_children <= 64, but got " + std::to_string(n_children) + ".");
+    if (!(std::isfinite(k) && k > 0.0f))
+        return fail(OAMD_INVALID_ARGUMENT, "Expected a finite forced playout factor k > 0, but got " + std::to_string(k) + ".");
+    if (n_children > 0 && (!visits || !q || !priors || !pruned_out))
+        return fail(OAMD_INVALID_ARGUMENT, "null array");
+    int64_t sum = 0;
+    int best = 0;
+    for (int j = 0; j < n_children; ++j) {
+        if (visits[j] < 0) return fail(OAMD_INVALID_ARGUMENT, "negative visit count");
+        pruned_out[j] = visits[j];
+        sum += visits[j];
+        if (visits[j] > visits[best]) best = j;
+    }
+    if (sum > INT32_MAX) return fail(OAMD_INVALID_ARGUMENT, "the visit counts' sum exceeds int32");
+    if (n_children <= 1 || sum == 0) return OAMD_OK;
+    const int32_t total = (int32_t)sum;
+    const float er = std::log(((float)(1 + root_visit_count) + c_puct_base) / c_puct_base) + c_puct_init;
+    const float mult = er * sqrtf((float)total);
+    const float ubest = prune_score(q[best], mult, priors[best], visits[best]);
+    for (int j = 0; j < n_children; ++j)
+        if (j != best) pruned_out[j] = prune_child(visits[j], q[j], priors[j], mult, ubest, k, total);
+    return OAMD_OK;
+}
+
 int oamd_engine_set_free_running(oamd_engine* e, int32_t enable) {
     e->free_running = enable != 0;
     return OAMD_OK;
@@ -1101,6 +1154,14 @@ int oamd_engine_game_key(oamd_engine* e, int32_t game, uint64_t* key) {
     if (game < 0 || game >= e->G) return fail(OAMD_OUT_OF_RANGE, "game index out of range");
     DeviceGuard dg(e->device);
     HIPCHK(hipMemcpyAsync(key, &e->games.get()[game].key, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return OAMD_OK;
+}
+
+int oamd_engine_game_event(oamd_engine* e, int32_t game, uint64_t* event) {
+    if (game < 0 || game >= e->G) return fail(OAMD_OUT_OF_RANGE, "game index out of range");
+    DeviceGuard dg(e->device);
+    HIPCHK(hipMemcpyAsync(event, &e->games.get()[game].event, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return OAMD_OK;
 }

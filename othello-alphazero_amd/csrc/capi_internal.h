@@ -170,6 +170,11 @@ struct oamd_engine {
         if (cap_fast > c.num_simulations) return "the playout cap's fast_simulations exceeds num_simulations";
         return nullptr;
     }
+    // forced playouts and policy target pruning (oamd_engine_set_forced_playouts,
+    // DESIGN.md §18): forced_k = 0 is off
+    float forced_k = 0.0f;
+    bool prune_targets = false;
+    bool forced_playouts() const { return forced_k > 0.0f; }
     // workgroups of an extra round's ResNet launch (0 = the regular grid)
     int extra_grid = 128;
     int step_phase = 0;  // 1 = a selected round awaits its backup (step API)
@@ -289,6 +294,8 @@ struct oamd_engine {
         E.terminal_skip = exact_interleaving ? 1 : 0;
         E.fast_steps = playout_cap() ? search_steps(cap_fast, L()) : 0;
         E.full_probability = cap_p;
+        E.forced_k = forced_k;
+        E.prune_targets = forced_playouts() && prune_targets ? 1 : 0;
         return E;
     }
 };

@@ -138,6 +138,9 @@ static int arena_checks(const oamd_engine* a, const oamd_engine* b) {
     // matches are played with full searches
     if (a->playout_cap() || b->playout_cap())
         return fail(OAMD_INVALID_ARGUMENT, "arena: an engine has a playout cap set (the arena does not use it)");
+    // ... and without forced playouts
+    if (a->forced_playouts() || b->forced_playouts())
+        return fail(OAMD_INVALID_ARGUMENT, "arena: an engine has forced playouts set (the arena does not use them)");
     return OAMD_OK;
 }
 

@@ -106,6 +106,12 @@ struct EngineView {
     // thread with no root noise
     int32_t fast_steps;
     float full_probability;
+    // forced playouts and policy target pruning (forced.h):
+    // forced_k = 0 is off; else a full search forces root children below their
+    // visit floor, and with prune_targets the self-play targets are written
+    // from the pruned counts
+    float forced_k;
+    int32_t prune_targets;
 };
 
 }  // namespace oamd

@@ -46,6 +46,8 @@ void launch_apply_actions(const EngineView& E, const int32_t* actions, hipStream
 void launch_apply_one(const EngineView& E, int g, int action, hipStream_t s);
 void launch_root_stats(const EngineView& E, int game_begin, int n_games, oamd_root_info* info,
                        int32_t* visits, float* q, int by_action, hipStream_t s);
+// (G, 65) stored priors of the root children by action, 0 where not a child
+void launch_root_priors(const EngineView& E, float* priors, hipStream_t s);
 void launch_self_play_data(const EngineView& E, int g, float* feat, float* pol, hipStream_t s);
 void launch_selfplay_move(const EngineView& E, const SelfplayParams& sp, int g0, int ng, int32_t* actions,
                           int32_t* finished, float* feat, float* pol, hipStream_t s);

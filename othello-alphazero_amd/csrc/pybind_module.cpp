@@ -456,6 +456,21 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
               return oamd_playout_cap_is_full(game_key, ply, full_probability) != 0;
           },
           "game_key"_a, "ply"_a, "full_probability"_a);
+    m.def("prune_visit_counts",
+          [](int root_visit_count, py::array_t<int32_t, py::array::c_style | py::array::forcecast> visits,
+             py::array_t<float, py::array::c_style | py::array::forcecast> q,
+             py::array_t<float, py::array::c_style | py::array::forcecast> priors, float c_puct_base,
+             float c_puct_init, float k) {
+              const py::ssize_t n = visits.size();
+              if (visits.ndim() != 1 || q.ndim() != 1 || priors.ndim() != 1 || q.size() != n || priors.size() != n)
+                  throw py::value_error("Expected visits, q and priors as 1-d arrays of one length.");
+              py::array_t<int32_t> out(n);
+              check(oamd_prune_visit_counts((int32_t)n, root_visit_count, visits.data(), q.data(), priors.data(),
+                                            c_puct_base, c_puct_init, k, out.mutable_data()));
+              return out;
+          },
+          "root_visit_count"_a, "visits"_a, "q"_a, "priors"_a, "c_puct_base"_a = 20000.0f, "c_puct_init"_a = 2.5f,
+          "k"_a = 2.0f);
     m.def("set_resnet_c128_four_wave", [](bool enable) { check(oamd_set_resnet_c128_four_wave(enable ? 1 : 0)); });
     m.def("resnet_c128_four_wave", []() { return oamd_resnet_c128_four_wave() != 0; });
     m.def("source_hash", [](const std::string& family) {
@@ -719,6 +734,20 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                  check(oamd_engine_game_key(e.h, game, &k));
                  return k;
              })
+        .def("game_event",
+             [](Engine& e, int game) {
+                 uint64_t ev;
+                 check(oamd_engine_game_event(e.h, game, &ev));
+                 return ev;
+             })
+        // forced playouts and policy target pruning (k 0 = off)
+        .def("set_forced_playouts",
+             [](Engine& e, float k, bool prune_targets) {
+                 const oamd_forced_playouts f{k, prune_targets ? 1 : 0};
+                 check(oamd_engine_set_forced_playouts(e.h, k == 0.0f ? nullptr : &f));
+             })
+        .def("root_priors",
+             [](Engine& e, uintptr_t priors) { check(oamd_engine_root_priors(e.h, reinterpret_cast<float*>(priors))); })
         .def("set_active",
              [](Engine& e, uintptr_t active) {
                  check(oamd_engine_set_active(e.h, reinterpret_cast<const uint8_t*>(active)));

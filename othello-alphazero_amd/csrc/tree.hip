@@ -19,6 +19,7 @@
 
 #include "bitboard.h"
 #include "engine.h"
+#include "forced.h"
 #include "kernels.h"
 #include "rng.h"
 
@@ -372,6 +373,12 @@ __device__ __forceinline__ void select_range(const EngineView& E, int g, GameSta
                     TS_ADD(kTsNoise, tn1 - tn0);
                 }
                 float ucb = cs.q + mult * prob / (1.0f + (float)cs.n);
+                // forced playouts (forced.h): at the root of a full
+                // search a tried child below its visit floor goes first (the
+                // lowest such child: the first-max argmax). Wave-uniform branch,
+                // E.forced_k read here from the kernel argument.
+                if (node == root && !fast && E.forced_k > 0.0f && forced_playout(cs.n, prob, total, E.forced_k))
+                    ucb = __builtin_inff();
                 if (lane >= nc) ucb = -__builtin_inff();
                 best = wave_argmax_first_n(ucb, nc);
             }  // a single child is taken without scoring (search_thread.cpp:194-196)
@@ -1138,9 +1145,59 @@ __global__ __launch_bounds__(64) void k_root_stats(EngineView E, int game_begin,
     }
 }
 
+// Stored priors of every game's root children by action (lane = square, pass
+// in slot 64), 0 where there is no child: the P of k_root_stats' N and Q.
+__global__ __launch_bounds__(64) void k_root_priors(EngineView E, float* priors) {
+    const int g = blockIdx.x;
+    const int lane = lane_id();
+    const size_t base = (size_t)g * E.cap;
+    const int root = E.games[g].root;
+    const NodeLink lk = load_link(E.link + base + root);
+    const uint64_t legal = E.pos[base + root].legal;
+    const int nc = lk.n_children;
+    float* po = priors + (size_t)g * 65;
+    float p = 0.0f, pass = 0.0f;
+    if (nc > 0) {
+        if (legal) {
+            if ((legal >> (63 - lane)) & 1ULL) p = E.stat[base + lk.first_child + child_index_of(legal, nc, lane)].p;
+        } else {
+            pass = E.stat[base + lk.first_child].p;
+        }
+    }
+    po[lane] = p;
+    if (lane == 0) po[64] = pass;
+}
+
+// Visit count of root child `lane` of game g as the policy target counts it
+// (0 for lanes past the children): the raw count, or with policy target pruning
+// (E.prune_targets, forced.h) the pruned one. The most visited
+// child (the first of them) keeps its count; every other child gives back the
+// visits PUCT alone would not have spent, judged with the stored priors, the
+// root's exploration rate and the children's visit sum as the selection uses
+// them. One wave, lane = child.
+__device__ __forceinline__ int root_target_count(const EngineView& E, int g) {
+    const int lane = lane_id();
+    const size_t base = (size_t)g * E.cap;
+    const int root = E.games[g].root;
+    const NodeLink lk = load_link(E.link + base + root);
+    const int nc = lk.n_children;
+    NodeStat cs{0, 0.0f, 0.0f, 0.0f};
+    if (lane < nc) cs = load_stat(E.stat + base + lk.first_child + lane);
+    if (!E.prune_targets || nc <= 1) return cs.n;
+    const int total = wave_sum(cs.n);
+    if (total == 0) return cs.n;
+    const int mx = wave_max_i(lane < nc ? cs.n : (int)0x80000000);
+    const int best = __ffsll((unsigned long long)__ballot(lane < nc && cs.n == mx)) - 1;
+    const float mult = explore_rate(E, E.stat[base + root].n) * sqrt_count(E, total);
+    const float ubest = readlane_f(prune_score(cs.q, mult, cs.p, cs.n), best);
+    if (lane < nc && lane != best) return prune_child(cs.n, cs.q, cs.p, mult, ubest, E.forced_k, total);
+    return cs.n;
+}
+
 // 8-fold self-play targets of the root (mcts.cpp:63-112): features of the root
-// under transform t (wave t of the block) and policy[transform(a,t)] = N_a/sum.
-__device__ void write_targets(const EngineView& E, int g, int t, float* feat_out, float* pol_out) {
+// under transform t (wave t of the block) and policy[transform(a,t)] = N_a/sum,
+// N = n of lane = child, the caller's root_target_count (computed once per root).
+__device__ void write_targets(const EngineView& E, int g, int t, int n, float* feat_out, float* pol_out) {
     const int lane = lane_id();
     const GameState* gs = E.games + g;
     const size_t base = (size_t)g * E.cap;
@@ -1166,8 +1223,6 @@ __device__ void write_targets(const EngineView& E, int g, int t, float* feat_out
     }
     float* po = pol_out + (size_t)t * 65;
     const int nc = lk.n_children;
-    int n = 0;
-    if (lane < nc) n = E.stat[base + lk.first_child + lane].n;
     int sum = wave_sum(n);
     if (sum == 0) sum = 1;
     po[lane] = 0.0f;
@@ -1188,7 +1243,7 @@ __device__ void write_targets(const EngineView& E, int g, int t, float* feat_out
 
 __global__ __launch_bounds__(512) void k_self_play_data(EngineView E, int g, float* feat_out,
                                                         float* pol_out) {
-    write_targets(E, g, threadIdx.x >> 6, feat_out, pol_out);
+    write_targets(E, g, threadIdx.x >> 6, root_target_count(E, g), feat_out, pol_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1326,8 +1381,9 @@ __device__ __forceinline__ void selfplay_move_game(const EngineView& E, const Se
         action = choose_root_action(E, gs, base, lk, rp, sp.temperature_moves, sp.temperature);
         if (sp.emit_targets && feat_out && nc > 0 && !fast) {
             const int C = 1 + 2 * E.H;
+            const int n = root_target_count(E, g);
             for (int t = 0; t < 8; ++t)
-                write_targets(E, g, t, feat_out + (size_t)g * 8 * C * 64, pol_out + (size_t)g * 8 * 65);
+                write_targets(E, g, t, n, feat_out + (size_t)g * 8 * C * 64, pol_out + (size_t)g * 8 * 65);
         }
         if (lane == 0) {
             gs->event = ev + 1;
@@ -1727,6 +1783,9 @@ void launch_apply_one(const EngineView& E, int g, int action, hipStream_t s) {
 void launch_root_stats(const EngineView& E, int game_begin, int n_games, oamd_root_info* info,
                        int32_t* visits, float* q, int by_action, hipStream_t s) {
     hipLaunchKernelGGL(k_root_stats, dim3(n_games), dim3(64), 0, s, E, game_begin, info, visits, q, by_action);
+}
+void launch_root_priors(const EngineView& E, float* priors, hipStream_t s) {
+    hipLaunchKernelGGL(k_root_priors, dim3(E.G), dim3(64), 0, s, E, priors);
 }
 void launch_self_play_data(const EngineView& E, int g, float* feat, float* pol, hipStream_t s) {
     hipLaunchKernelGGL(k_self_play_data, dim3(1), dim3(512), 0, s, E, g, feat, pol);

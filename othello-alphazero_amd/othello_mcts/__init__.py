@@ -22,6 +22,9 @@ at K empties with the exact result. ``BatchedMCTS.set_playout_cap`` switches on
 playout cap randomization (full searches recorded, fast ones only played:
 ``FIN_FAST``, ``playout_cap_is_full``), and ``selfplay_steps(sim_budget=...)``
 gives every game of a free-running call a work budget instead of a move count.
+``BatchedMCTS.set_forced_playouts`` switches on forced playouts at the root of
+full searches and policy target pruning (``prune_visit_counts`` is the pruning
+rule on the host).
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -40,6 +43,7 @@ from ._othello_mcts_impl import (  # noqa: F401
     get_flips,
     get_legal_moves,
     playout_cap_is_full,
+    prune_visit_counts,
 )
 from .batched import BatchedMCTS  # noqa: E402,F401
 from .arena import Arena, ArenaResult, paired_openings  # noqa: E402,F401
@@ -83,4 +87,5 @@ __all__ = [
     "adjudicate",
     "FIN_FAST",
     "playout_cap_is_full",
+    "prune_visit_counts",
 ]

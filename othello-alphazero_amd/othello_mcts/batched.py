@@ -10,6 +10,8 @@ single-game semantics (tested against the oracle game by game).
 
 from __future__ import annotations
 
+import math
+
 import torch
 
 from ._othello_mcts_impl import SearchConfig, _Engine
@@ -156,6 +158,36 @@ class BatchedMCTS:
             raise ValueError(f"Expected 1 <= fast_simulations <= num_simulations ({self.config.num_simulations}), "
                              f"but got {fast_simulations}.")
         self.engine.set_playout_cap(p, n)
+
+    def set_forced_playouts(self, k: float | None = None, prune_targets: bool = True) -> None:
+        """Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2;
+        DESIGN.md §18). With ``k`` set, the root of every full search (never a
+        fast one of a playout cap) takes a child that has been tried first while
+        ``n_c * n_c < (k * prob_c) * total`` (fp32; ``prob_c`` the prior of that
+        selection's PUCT line, noised when the root draws noise; ``total`` the
+        children's visits with in-flight ones): every tried child keeps a floor
+        of ``sqrt(k * prob_c * total)`` visits. With ``prune_targets`` the
+        self-play targets are written from ``othello_mcts.prune_visit_counts`` of
+        the root instead of the raw counts: the visits PUCT alone would not have
+        spent are taken out, and a child left with one is dropped. Visit counts
+        and Q as queried, the move choice and ``finished`` do not change; no
+        random event is consumed. ``None``: off, the default. KataGo uses k = 2.
+        The arena does not use the setting and rejects an engine that has it."""
+        if k is None:
+            self.engine.set_forced_playouts(0.0, False)
+            return
+        kf = float(k)
+        if not (math.isfinite(kf) and kf > 0.0):
+            raise ValueError(f"Expected a finite forced playout factor k > 0, but got {k}.")
+        self.engine.set_forced_playouts(kf, bool(prune_targets))
+
+    def root_priors(self) -> torch.Tensor:
+        """Stored priors of every game's root children, (G, 65) indexed by action
+        like ``root_stats`` (0 where there is no child)."""
+        self._stream()
+        p = torch.empty((self.num_games, 65), dtype=torch.float32, device=self.device)
+        self.engine.root_priors(p.data_ptr())
+        return p
 
     def random_openings(self, max_moves: int = 8, seed: int = 0) -> None:
         self._stream()

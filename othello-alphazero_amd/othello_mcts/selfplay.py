@@ -125,7 +125,7 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
               opening_moves: int = 0, device: str | torch.device = "cpu",
               moves_per_call: int = 16, adjudicate_empties: int = 0,
               split: bool = False, playout_cap: tuple[float, int] | None = None,
-              sim_budget: int = 0) -> dict[str, list[torch.Tensor]]:
+              sim_budget: int = 0, forced_playouts: float | None = None) -> dict[str, list[torch.Tensor]]:
     """Play until at least ``games`` games have completed across the batch (each
     slot restarts when its game ends) and return their samples in the
     reference's ``_self_play`` format (train.py:404-452). ``opening_moves=0``
@@ -153,13 +153,20 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
     samples. sim_budget = S > 0 (native net, moves_per_call > 1): every call
     gives each game S nominal simulations instead of ``moves_per_call`` moves
     (``BatchedMCTS.selfplay_steps``); ``moves_per_call`` is then the slot count,
-    the most moves of a game per call."""
+    the most moves of a game per call.
+
+    forced_playouts = k: sets the engine's forced playouts with policy target
+    pruning for this run (``BatchedMCTS.set_forced_playouts(k)``, DESIGN.md §18;
+    None leaves the engine as it is). The policy samples are then the pruned
+    targets; nothing else about the samples changes."""
     from .adjudication import check_adjudicate_empties
     from .native import resolve
 
     check_adjudicate_empties(adjudicate_empties)
     if playout_cap is not None:
         batched.set_playout_cap(*playout_cap)
+    if forced_playouts is not None:
+        batched.set_forced_playouts(forced_playouts)
     sim_budget = int(sim_budget)
     if sim_budget < 0:
         raise ValueError(f"Expected sim_budget >= 0, but got {sim_budget}.")

@@ -13,7 +13,7 @@ descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
 Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds]
-                 [packed [exact=K]] [adjudicate=K] [split] [cap=P:N] [budget=S]
+                 [packed [exact=K]] [adjudicate=K] [split] [cap=P:N] [budget=S] [forced=K]
 
 packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
 million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
@@ -41,6 +41,9 @@ else N simulations, played but not recorded. budget=S: every selfplay_steps
 call gives each game S nominal simulations instead of 16 moves
 (selfplay_steps(sim_budget=S)); the call's slot count is the most moves S buys
 (S / N rounded up with a cap, S / 800 without), 64 at the most.
+
+forced=K: forced playouts at the root of full searches with factor K and policy
+target pruning (BatchedMCTS.set_forced_playouts(K); KataGo: 2).
 
 new_positions (packed) is the ring head's advance, valid while one iteration
 stores fewer positions than the ring holds; new_games / selfplay_s and
@@ -122,6 +125,8 @@ def main():
     cap = (float(cap[0][0]), int(cap[0][1])) if cap else None
     budget = [int(w[7:]) for w in sys.argv[5:] if w.startswith("budget=")]
     budget = budget[0] if budget else 0
+    forced = [float(w[7:]) for w in sys.argv[5:] if w.startswith("forced=")]
+    forced = forced[0] if forced else None
     L = 2 * 16
     nominal_min = -(-(cap[1] if cap else 800) // L) * L  # the smallest search's nominal simulations
     slots = min(64, -(-budget // nominal_min)) if budget else 16
@@ -138,6 +143,8 @@ def main():
     b.reset()
     if cap:
         b.set_playout_cap(*cap)
+    if forced:
+        b.set_forced_playouts(forced)
     if packed:
         buf = om.ReplayBuffer(G, 8, capacity=500_000, device=dev, track_exact=bool(exact))
     else:
@@ -209,7 +216,8 @@ def main():
                                                     "exact_max_empties": exact[0] if exact else None,
                                                     "exact_split": split and bool(exact),
                                                     "adjudicate_empties": K, "adjudicate_split": split and K > 0,
-                                                    "playout_cap": cap, "sim_budget": budget, "slots_per_call": slots},
+                                                    "playout_cap": cap, "sim_budget": budget, "slots_per_call": slots,
+                                                    "forced_playouts": forced},
                                                    indent=1))
 
 
