@@ -82,6 +82,38 @@ int oamd_debug_read_stamps(uint64_t *out, int64_t n);
  * buffer (the outputs of the native search's ResNet launches); *intact = 1
  * while no launch has written any of them (waits for the device). */
 int oamd_debug_eval_guards(oamd_engine *e, int32_t *intact);
+/* Diagnostics, for tests/test_gpu_resnet_packed.py: the native search's ResNet
+ * launch (bit-packed feature rows read through an evaluation list) on the
+ * caller's rows. feat_dev: feat_rows rows of 2 + 2 * history words (history in
+ * [1, 15], the net's in_channels = 1 + 2 * history), in the engine's layout:
+ * word 0 = meta (bit 0 the player plane, bits 8-10 the board symmetry, bit 16
+ * valid; an invalid row is evaluated as an all-zero board, or not at all when
+ * every row of its workgroup is invalid), word 1 = 0, words 2 + 2h / 3 + 2h
+ * the two disc sets of position h. policy_dev / value_dev: out_rows rows of 65
+ * floats / out_rows floats; launch entry i writes row list[i] of both.
+ * list_host = NULL (list_len = list_off = 0, count ignored): the dense launch
+ * of rows 0 .. rows-1. Otherwise list_host holds list_len row indices and the
+ * launch is the engine's: entries list_off .. list_off + rows - 1 of the list,
+ * of which those below `count` (the list's filled entries, counted from entry
+ * 0) are evaluated. The list and the count are copied into device memory the
+ * net owns. max_wgs > 0 caps the grid: the workgroups loop over the board
+ * groups (the extra rounds' launch); 0 = one workgroup per board group.
+ * Nothing is launched (OAMD_INVALID_ARGUMENT) unless history, the net's
+ * in_channels and the sizes agree, rows >= 0, count >= 0, max_wgs >= 0,
+ * list_off >= 0 and list_off + rows <= list_len, every list entry (dense:
+ * every row below `rows`) is in [0, min(feat_rows, out_rows)), and the
+ * buffers a launch would touch are not NULL. Waits for the device before it
+ * replaces the list of the previous call; the launch itself is asynchronous
+ * on `stream`. */
+int oamd_debug_forward_packed(oamd_net *net, const uint64_t *feat_dev, int64_t feat_rows, int32_t history,
+                              const int32_t *list_host, int32_t list_len, int32_t count, int32_t list_off,
+                              int32_t rows, int32_t max_wgs, float *policy_dev, float *value_dev, int64_t out_rows,
+                              void *stream);
+/* Diagnostics: copy the engine's packed feature rows (num_games x num_threads
+ * x batch_size rows of 2 + 2 * history_size words, as the last select left
+ * them) into out_dev, which holds `words` words: exactly that many, else
+ * OAMD_INVALID_ARGUMENT. Waits for the engine's stream. */
+int oamd_debug_engine_feature_rows(oamd_engine *e, uint64_t *out_dev, int64_t words);
 /* Diagnostics: k_tree's phase cycle sums over every wave since the last reset
  * (tools/tree_stamps.py); reset != 0 zeroes them after the copy. Only in
  * builds with OAMD_EXTRA_FLAGS=-DOAMD_TREE_STAMPS; otherwise

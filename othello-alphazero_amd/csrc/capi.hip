@@ -675,6 +675,19 @@ int oamd_debug_eval_guards(oamd_engine* e, int32_t* intact) {
     return OAMD_OK;
 }
 
+int oamd_debug_engine_feature_rows(oamd_engine* e, uint64_t* out_dev, int64_t words) {
+    if (!e || !out_dev) return fail(OAMD_INVALID_ARGUMENT, "feature rows: null argument");
+    const int64_t have = (int64_t)e->G * e->L() * e->FW();
+    if (words != have)
+        return fail(OAMD_INVALID_ARGUMENT, "feature rows: expected a buffer of " + std::to_string(have) +
+                                               " words, got " + std::to_string(words));
+    DeviceGuard dg(e->device);
+    HIPCHK(hipMemcpyAsync(out_dev, e->rows.feat.get(), (size_t)have * sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return OAMD_OK;
+}
+
 int oamd_debug_read_stamps(uint64_t* out, int64_t n) {
     if (!out || n < 0) return fail(OAMD_INVALID_ARGUMENT, "stamps: bad buffer");
     const int rc = resnet_read_stamps(reinterpret_cast<unsigned long long*>(out), (long long)n);

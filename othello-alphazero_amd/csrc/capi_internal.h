@@ -311,6 +311,9 @@ struct oamd_net {
     oamd::DeviceBuf<float> head;
     oamd::DeviceBuf<uint16_t> hconv;
     bool loaded = false;
+    // oamd_debug_forward_packed: its evaluation list, the counter behind it
+    oamd::DeviceBuf<int32_t> debug_list;
+    int64_t debug_list_cap = 0;
     std::vector<std::string> keys;
     std::vector<int64_t> numel;
 

@@ -243,4 +243,56 @@ int oamd_net_forward(oamd_net* net, const float* features, int32_t rows, float* 
     return OAMD_OK;
 }
 
+int oamd_debug_forward_packed(oamd_net* net, const uint64_t* feat_dev, int64_t feat_rows, int32_t history,
+                              const int32_t* list_host, int32_t list_len, int32_t count, int32_t list_off,
+                              int32_t rows, int32_t max_wgs, float* policy_dev, float* value_dev, int64_t out_rows,
+                              void* stream) {
+    if (!net || !net->loaded) return fail(OAMD_INVALID_ARGUMENT, "forward_packed: net weights not loaded");
+    if (history < 1 || history > kMaxHistory)
+        return fail(OAMD_INVALID_ARGUMENT, "forward_packed: history must be in [1, 15], got " + std::to_string(history));
+    if (net->desc.in_channels != 1 + 2 * history)
+        return fail(OAMD_INVALID_ARGUMENT, "forward_packed: net in_channels != 1 + 2 * history");
+    if (feat_rows < 0 || out_rows < 0 || rows < 0 || max_wgs < 0 || count < 0)
+        return fail(OAMD_INVALID_ARGUMENT, "forward_packed: negative size");
+    // every row a launch can read or write lies below this
+    const int64_t bound = std::min(feat_rows, out_rows);
+    if (list_host) {
+        if (list_len < 0 || list_off < 0 || (int64_t)list_off + rows > (int64_t)list_len)
+            return fail(OAMD_INVALID_ARGUMENT, "forward_packed: list_off + rows exceeds list_len");
+        for (int32_t i = 0; i < list_len; ++i)
+            if (list_host[i] < 0 || list_host[i] >= bound)
+                return fail(OAMD_INVALID_ARGUMENT, "forward_packed: list entry " + std::to_string(i) + " = " +
+                                                       std::to_string(list_host[i]) + " is not a row of both buffers");
+    } else {
+        if (list_len != 0 || list_off != 0)
+            return fail(OAMD_INVALID_ARGUMENT, "forward_packed: list_len and list_off must be 0 without a list");
+        if (rows > bound) return fail(OAMD_INVALID_ARGUMENT, "forward_packed: rows exceeds feat_rows or out_rows");
+    }
+    if (rows == 0) return OAMD_OK;
+    if (!feat_dev || !policy_dev || !value_dev) return fail(OAMD_INVALID_ARGUMENT, "forward_packed: null buffer");
+    DeviceGuard dg(net->device);
+    const int32_t* list_dev = nullptr;
+    const int32_t* count_dev = nullptr;
+    if (list_host) {
+        // the previous call's launch may still read the list (any stream)
+        HIPCHK(hipDeviceSynchronize());
+        if ((int64_t)list_len + 1 > net->debug_list_cap) {
+            net->debug_list_cap = 0;
+            if (int rc = net->debug_list.alloc((size_t)list_len + 1)) return rc;
+            net->debug_list_cap = (int64_t)list_len + 1;
+        }
+        // [0] the counter, [1 ..] the list
+        HIPCHK(hipMemcpy(net->debug_list.get(), &count, sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(net->debug_list.get() + 1, list_host, (size_t)list_len * sizeof(int32_t),
+                         hipMemcpyHostToDevice));
+        HIPCHK(hipDeviceSynchronize());
+        count_dev = net->debug_list.get();
+        list_dev = net->debug_list.get() + 1 + list_off;
+    }
+    launch_resnet_packed(net->view(), feat_dev, feature_words(history), history, rows, policy_dev, value_dev,
+                         (hipStream_t)stream, list_dev, count_dev, list_off, nullptr, max_wgs);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
 }  // extern "C"

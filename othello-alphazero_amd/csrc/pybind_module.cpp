@@ -1020,4 +1020,26 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
         check(oamd_apply_action((const oamd_position*)in, (const int32_t*)actions, (oamd_position*)out, n,
                                 (void*)stream));
     });
+
+    // the packed ResNet launch on caller-supplied rows (tests/test_gpu_resnet_packed.py);
+    // list None = the dense launch
+    m.def("_debug_forward_packed",
+          [](Net& net, uintptr_t feat, int64_t feat_rows, int history, py::object list, int count, int list_off,
+             int rows, int max_wgs, uintptr_t policy, uintptr_t value, int64_t out_rows, uintptr_t stream) {
+              std::vector<int32_t> l;
+              const bool dense = list.is_none();
+              if (!dense) l = list.cast<std::vector<int32_t>>();
+              // a list without entries is still a list: never NULL
+              const int32_t none = 0;
+              check(oamd_debug_forward_packed(net.h, reinterpret_cast<const uint64_t*>(feat), feat_rows, history,
+                                              dense ? nullptr : (l.empty() ? &none : l.data()), (int32_t)l.size(),
+                                              count, list_off, rows, max_wgs, reinterpret_cast<float*>(policy),
+                                              reinterpret_cast<float*>(value), out_rows,
+                                              reinterpret_cast<void*>(stream)));
+          },
+          "net"_a, "features"_a, "feat_rows"_a, "history"_a, "list"_a, "count"_a, "list_off"_a, "rows"_a,
+          "max_wgs"_a, "policy"_a, "value"_a, "out_rows"_a, "stream"_a = 0);
+    m.def("_debug_engine_feature_rows", [](Engine& e, uintptr_t out, int64_t words) {
+        check(oamd_debug_engine_feature_rows(e.h, reinterpret_cast<uint64_t*>(out), words));
+    });
 }

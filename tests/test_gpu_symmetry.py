@@ -15,9 +15,10 @@ counts as lists, Q bits, 8-fold targets and feature rows with
 assert_array_equal. Reference: search_thread.cpp:59-148, transformation.h:40-116.
 
 All searches take the callback path (host evaluator). The packed ResNet
-prologue's own inverse_transform (csrc/resnet.hip) is tied to k_features_f32 by
-the native == callback tests with random nets (test_gpu_configs.py,
-test_gpu_resnet.py), which are not repeated here.
+prologue's own inverse_transform (csrc/resnet.hip) is pinned at the kernel by
+tests/test_gpu_resnet_packed.py: packed rows under every symmetry against the
+exact nets and, bit for bit, against the fp32-plane path, and the engine's own
+rows against k_features_f32.
 """
 
 import numpy as np
