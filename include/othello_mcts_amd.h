@@ -658,6 +658,59 @@ int oamd_replay_relabel_endgames_split(const oamd_replay_view *view, int8_t *exa
                                        int64_t node_limit, int32_t policy_mode, int32_t retry, void *workspace_dev,
                                        void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Exact leaf values (opt-in, off by default): the search     */
+/* solves leaves with few empties instead of asking the net.                 */
+/* ------------------------------------------------------------------------ */
+/* With max_empties = E in 1..10, wherever the search runs (the step API and
+ * the native schedules):
+ *  - a child created by an expansion that is not terminal and has at most E
+ *    empties is an exact leaf. It is never expanded and never evaluated;
+ *  - a node that becomes a game's root (a self-play move, oamd_engine_apply_
+ *    action(s), a restart or reset) loses the mark: the root is an ordinary
+ *    leaf that the net evaluates and expands;
+ *  - a descent that ends at an exact leaf is handled like one ending at a
+ *    terminal leaf: no NN row (oamd_engine_leaf_flags reports 0), no random
+ *    event, not an evaluation. The first visit solves the leaf with the
+ *    endgame solver's state machine, s = the sign of the exact disc difference
+ *    for the leaf's side to move under best play; the backup gives every node
+ *    on the path what a terminal leaf whose score for the parent's player is
+ *    -s would give, and the leaf keeps s for every later visit;
+ *  - a batch needs the evaluation round trip if it holds an NN row or a leaf
+ *    that is not solved yet; terminal and solved leaves alone are backed up
+ *    at once, as all-terminal batches are.
+ * One game with num_threads > 1 runs on the grouped schedule instead of the
+ * thread-split one (same results). E = 0 is off: no mark is ever written and
+ * nothing is launched, the engine is bit for bit the engine without the
+ * setting. The value may change only while no game holds a tree built under
+ * another value, i.e. before the first search or after oamd_engine_reset of
+ * all games (game = -1) or oamd_engine_random_openings: OAMD_INVALID_ARGUMENT
+ * otherwise, and for E outside 0..10. Independent of the playout cap, forced
+ * playouts and adjudication. The arena rejects an engine that has it. */
+int oamd_engine_set_exact_leaves(oamd_engine *e, int32_t max_empties);
+/* Since the engine was created (host outputs; waits for the engine's stream):
+ * solves = rows that ended at a leaf not solved yet (each is solved, also two
+ * rows at the same leaf in one round), hits = rows that ended at a solved
+ * leaf, nodes = positions the solves visited. */
+int oamd_engine_exact_leaf_counters(oamd_engine *e, int64_t *solves, int64_t *hits, int64_t *nodes);
+/* Rows that were backed up while their exact leaf had no result (host output;
+ * waits for the engine's stream): the solve kernel was not enqueued between
+ * the row's selection and its backup, or could not take the row. Such a row
+ * backs up a draw. Always 0 unless the host layer or the tree is broken; the
+ * Python layer's check_health raises on it. */
+int oamd_engine_exact_leaf_faults(oamd_engine *e, int64_t *faults);
+/* The rule on the host: *sign_or_none = s (-1, 0, +1) when the position would
+ * be an exact leaf at max_empties (1..10): not terminal and at most that many
+ * empties; OAMD_SOLVE_NONE otherwise (a position where neither side can move
+ * is terminal whatever `player` says). legal_moves / next_legal_moves are
+ * ignored. Every root action (the pass when the mover has no move) is searched
+ * with the window [-1, 1]. */
+int oamd_exact_leaf_sign(const oamd_position *pos_host, int32_t max_empties, int32_t *sign_or_none);
+/* The solve kernel's path over n positions on the device: sign_dev (n) as
+ * above, nodes_dev (n, may be NULL). Enqueued only. */
+int oamd_exact_leaf_signs(int32_t device, const oamd_position *pos_dev, int64_t n, int32_t max_empties,
+                          int32_t *sign_dev, int64_t *nodes_dev, void *stream);
+
 /* Timing accumulated over the timed oamd_engine_search calls (HIP events on
  * the launching streams; a query waits for the searches still in flight):
  * total ms spent in the NN kernel, number of NN launches, rows launched

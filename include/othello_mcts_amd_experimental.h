@@ -162,6 +162,13 @@ int oamd_solve_endgames_split_grid(int32_t device, const oamd_position *pos_dev,
  * steps enqueued before it are not timed (0 ms). Waits for the timed step. */
 int oamd_engine_adjudicate_ms(oamd_engine *e, float *ms, int64_t *resolves);
 
+/* oamd_exact_leaf_sign that also returns the positions the solve visited: the
+ * figure the device adds to the engine's solver-node counter for that leaf
+ * (oamd_engine_exact_leaf_counters). For tests and reports that account for
+ * the counters; nodes may be NULL. */
+int oamd_exact_leaf_sign_nodes(const oamd_position *pos_host, int32_t max_empties, int32_t *sign_or_none,
+                               int64_t *nodes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
-  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip, adjudicate.hip) + the C ABI
+  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip, adjudicate.hip,
+                           exact_leaves.hip) + the C ABI
                            (capi.hip and, by subsystem, capi_net.hip, capi_play.hip, capi_data.hip; capi_version.hip
                            carries the source hashes), hipcc --offload-arch=gfx950
   _othello_mcts_impl*.so   pybind11 host layer (pybind_module.cpp) over the C ABI
@@ -61,6 +62,9 @@ UNITS = {
     "solver.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # adjudication's apply kernel: integer code
     "adjudicate.hip": [],
+    # exact leaf values: the solver's integer code on a 10-level
+    # LDS stack; the build fails if a solve kernel reports any scratch
+    "exact_leaves.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 
@@ -80,9 +84,10 @@ def run(cmd: list[str]) -> None:
         raise SystemExit(f"build failed: {cmd[-1]}")
     if "kernel-resource-usage" in " ".join(cmd):
         # the remarks of a unit are checked by that unit's rule only
-        unit = next((u for u in RESOURCE_CHECKS if str(CSRC / u) in cmd), None)
+        checks = {**RESOURCE_CHECKS, **SCRATCH_CHECKS}
+        unit = next((u for u in checks if str(CSRC / u) in cmd), None)
         if unit:
-            RESOURCE_CHECKS[unit](r.stderr)
+            checks[unit](r.stderr)
     elif r.stderr.strip():
         sys.stderr.write(r.stderr)
 
@@ -157,7 +162,23 @@ def check_resnet(remarks: str) -> None:
     check_w4_resources(remarks)
 
 
+def check_exact_leaves_scratch(remarks: str) -> None:
+    """exact_leaves.hip: k_solve_leaves and k_solve_positions keep their
+    searcher stacks in LDS (17,920 bytes per wave); fail on any scratch."""
+    seen = 0
+    for name, field, value in kernel_remarks(remarks):
+        if "k_solve" in name and field.startswith("ScratchSize"):
+            seen += 1
+            if int(value.split()[0]) != 0:
+                raise SystemExit(f"build failed: {name} uses {value} bytes of scratch per lane: "
+                                 "the exact-leaf solver's stack must stay in LDS")
+    if not seen:
+        raise SystemExit("build failed: no resource remark for k_solve_leaves in exact_leaves.hip")
+
+
 RESOURCE_CHECKS = {"resnet.hip": check_resnet, "solver.hip": check_solver_scratch}
+# units whose every search kernel must stay without scratch (its stack is LDS)
+SCRATCH_CHECKS = {"exact_leaves.hip": check_exact_leaves_scratch}
 
 
 def newer(out: Path, deps: list[Path]) -> bool:

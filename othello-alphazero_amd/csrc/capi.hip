@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "capi_internal.h"
+#include "exact_leaf.h"
 #include "forced.h"
 #include "rng.h"
 
@@ -222,6 +223,7 @@ int oamd_engine_reset(oamd_engine* e, int32_t game, uint64_t seed) {
     launch_reset(e->view(), game, seed, e->stream);
     LAUNCHCHK();
     e->end_search();
+    if (game < 0) e->exact_trees = false;  // no tree left: the exact-leaf setting may change again
     return OAMD_OK;
 }
 
@@ -241,7 +243,10 @@ int oamd_engine_select(oamd_engine* e) {
     // next batch right after its backup (the reference's interleaving, k_tree)
     launch_tree(e->view(), e->stream, e->step_phase == 1, true, e->cfg.num_threads, e->cfg.batch_size, 0, -1, 0, -1,
                 nullptr, nullptr, e->steps_left == e->steps_total);
+    // exact leaves: the round's pending leaves are solved before its backup
+    launch_solve_leaves(e->view(), 0, e->G * e->L(), e->stream);
     LAUNCHCHK();
+    e->exact_trees = true;
     e->step_phase = 1;
     e->steps_left -= 1;
     return OAMD_OK;
@@ -418,6 +423,14 @@ static int enqueue_group_nn(oamd_engine* e, const EngineView& E, const NetView& 
                             bool wait_token, const Event* ev, int* count, unsigned long long* span, int max_wgs) {
     hipStream_t sk = P.st[k];
     hipEvent_t token = e->pipe.nn_token[k % std::min(e->nn_chains, P.K)].get();
+    // exact leaves: the group's pending leaves are solved
+    // between its tree launch and the next one. Before the wait for the NN
+    // token, so the solve waves run beside the other group's ResNet launch as
+    // the tree waves do (measured against a launch behind this group's ResNet
+    // launches). It lies between the block's tree-end and
+    // NN-begin events: a timed search counts it in neither. Nothing is
+    // launched with the setting off.
+    launch_solve_leaves(E, P.g0[k] * E.L, P.ng[k] * E.L, sk);
     if (P.K > 1 && wait_token) HIPCHK(hipStreamWaitEvent(sk, token, 0));
     if (ev) HIPCHK(hipEventRecord(ev[2].get(), sk));
     const int grows = P.ng[k] * E.L, cb = launch_rows(grows, e->nn_batch);
@@ -597,6 +610,7 @@ int oamd_engine_search(oamd_engine* e, oamd_net* net, int64_t* sims, int64_t* ev
     DeviceGuard dg(e->device);
     if (sims || evals) HIPCHK(hipMemsetAsync(e->counters.get(), 0, 2 * sizeof(unsigned long long), e->stream));
     const NetView N = net->view();
+    e->exact_trees = true;
     if (int rc = e->thread_split() ? search_thread_split(e, N) : search_grouped(e, N)) return rc;
     // without counters requested the search is left in flight (stream order)
     if (sims || evals) {
@@ -1048,6 +1062,77 @@ int oamd_prune_visit_counts(int32_t n_children, int32_t root_visit_count, const 
     return OAMD_OK;
 }
 
+// ---------------------------------------------------------------- exact leaves
+int oamd_engine_set_exact_leaves(oamd_engine* e, int32_t max_empties) {
+    if (max_empties < 0 || max_empties > kExactMaxEmpties)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 0 <= max_empties <= " + std::to_string(kExactMaxEmpties) +
+                                               " (0 = off), but got " + std::to_string(max_empties) + ".");
+    if (!exact_setting_change_ok(e->exact_empties, max_empties, e->exact_trees))
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "exact leaves: the setting cannot change from " + std::to_string(e->exact_empties) + " to " +
+                        std::to_string(max_empties) +
+                        " while games hold trees built under the old value (reset all games first)");
+    e->exact_empties = max_empties;
+    e->end_search();
+    return OAMD_OK;
+}
+
+int oamd_engine_exact_leaf_counters(oamd_engine* e, int64_t* solves, int64_t* hits, int64_t* nodes) {
+    DeviceGuard dg(e->device);
+    unsigned long long c[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(c, e->counters.get() + 12, sizeof(c), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (solves) *solves = (int64_t)c[0];
+    if (hits) *hits = (int64_t)c[1];
+    if (nodes) *nodes = (int64_t)c[2];
+    return OAMD_OK;
+}
+
+int oamd_engine_exact_leaf_faults(oamd_engine* e, int64_t* faults) {
+    DeviceGuard dg(e->device);
+    unsigned long long c = 0;
+    HIPCHK(hipMemcpyAsync(&c, e->counters.get() + 15, sizeof(c), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (faults) *faults = (int64_t)c;
+    return OAMD_OK;
+}
+
+static int exact_empties_checks(int32_t max_empties) {
+    if (max_empties < 1 || max_empties > kExactMaxEmpties)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 1 <= max_empties <= " + std::to_string(kExactMaxEmpties) +
+                                               ", but got " + std::to_string(max_empties) + ".");
+    return OAMD_OK;
+}
+
+int oamd_exact_leaf_sign_nodes(const oamd_position* pos, int32_t max_empties, int32_t* sign_or_none, int64_t* nodes) {
+    if (!pos || !sign_or_none) return fail(OAMD_INVALID_ARGUMENT, "exact leaf sign: null argument");
+    if (int rc = exact_empties_checks(max_empties)) return rc;
+    if ((pos->player1_discs & pos->player2_discs) != 0 || pos->player < 0 || pos->player > 2)
+        return fail(OAMD_INVALID_ARGUMENT, "exact leaf sign: not a position (overlapping discs or a bad player)");
+    int32_t s = 0;
+    int64_t n = 0;
+    const bool is_leaf = exact_leaf_host(pos->player, pos->player1_discs, pos->player2_discs, max_empties, &s, &n);
+    *sign_or_none = is_leaf ? s : OAMD_SOLVE_NONE;
+    if (nodes) *nodes = is_leaf ? n : 0;
+    return OAMD_OK;
+}
+
+int oamd_exact_leaf_sign(const oamd_position* pos, int32_t max_empties, int32_t* sign_or_none) {
+    return oamd_exact_leaf_sign_nodes(pos, max_empties, sign_or_none, nullptr);
+}
+
+int oamd_exact_leaf_signs(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t max_empties,
+                          int32_t* sign_dev, int64_t* nodes_dev, void* stream) {
+    if (n < 0) return fail(OAMD_INVALID_ARGUMENT, "n must be >= 0");
+    if (int rc = exact_empties_checks(max_empties)) return rc;
+    if (n > 0 && (!pos_dev || !sign_dev)) return fail(OAMD_INVALID_ARGUMENT, "exact leaf signs: null array");
+    if (int rc = create_device_checks(device)) return rc;
+    DeviceGuard dg(device);
+    launch_solve_positions(pos_dev, n, max_empties, sign_dev, nodes_dev, (hipStream_t)stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
 int oamd_engine_set_free_running(oamd_engine* e, int32_t enable) {
     e->free_running = enable != 0;
     return OAMD_OK;
@@ -1068,6 +1153,7 @@ static int selfplay_steps_enqueue(oamd_engine* e, oamd_net* net, const SelfplayP
     };
     GroupPlan P = plan_groups(e);
     const bool split = e->thread_split();
+    e->exact_trees = true;
     if (!split && e->free_running) {
         if (int rc = e->pipe.ensure(P.K, P.K)) return rc;
         return selfplay_steps_free(e, net, sp, n_moves, per_move_outputs, actions_dev, finished_dev, features_dev,

@@ -65,8 +65,11 @@ constexpr int kEvPerBlock = 4;  // timing events per (round, group): tree begin/
 // device counters (k_tree): [0..1] sims / NN rows of the current search,
 // [2..3] cumulative, [4..5] of timed searches, [6] summed descent depths,
 // [7] deepest descent, [8..11] the tree work of oamd_engine_tree_work
-// (children scanned, expansions, children created, tree launches)
-constexpr int kCounters = 12;
+// (children scanned, expansions, children created, tree launches),
+// [12..14] exact leaves (oamd_engine_exact_leaf_counters): solves (the solve
+// kernel), hits of solved leaves (k_tree), solver nodes (the solve kernel);
+// [15] exact-leaf faults: rows backed up while still pending (k_tree)
+constexpr int kCounters = 16;
 
 struct DeviceGuard {
     int prev = -1;
@@ -175,6 +178,12 @@ struct oamd_engine {
     float forced_k = 0.0f;
     bool prune_targets = false;
     bool forced_playouts() const { return forced_k > 0.0f; }
+    // exact leaf values (oamd_engine_set_exact_leaves): 0 is off.
+    // exact_trees: a search ran since the last reset of all games, so some
+    // tree was built under the current value and the value may not change
+    int exact_empties = 0;
+    bool exact_trees = false;
+    bool exact_leaves() const { return exact_empties > 0; }
     // workgroups of an extra round's ResNet launch (0 = the regular grid)
     int extra_grid = 128;
     int step_phase = 0;  // 1 = a selected round awaits its backup (step API)
@@ -259,7 +268,8 @@ struct oamd_engine {
             const char* e = getenv("OAMD_TREE_SPLIT");
             return e ? atoi(e) != 0 : true;
         }();
-        return v && thread_split_shape(G, cfg.num_threads);
+        // exact leaves run on the grouped schedule, whose rounds carry the solve kernel
+        return v && !exact_leaves() && thread_split_shape(G, cfg.num_threads);
     }
     int FW() const { return oamd::feature_words(cfg.history_size); }
 
@@ -296,6 +306,8 @@ struct oamd_engine {
         E.full_probability = cap_p;
         E.forced_k = forced_k;
         E.prune_targets = forced_playouts() && prune_targets ? 1 : 0;
+        E.exact_empties = exact_empties;
+        E.exact = rows.exact.get();
         return E;
     }
 };

@@ -122,6 +122,7 @@ int oamd_engine_random_openings(oamd_engine* e, int32_t max_moves, uint64_t seed
     DeviceGuard dg(e->device);
     launch_random_openings(e->view(), max_moves, seed, e->stream);
     LAUNCHCHK();
+    e->exact_trees = false;  // every game was reset
     return OAMD_OK;
 }
 
@@ -141,6 +142,9 @@ static int arena_checks(const oamd_engine* a, const oamd_engine* b) {
     // ... and without forced playouts
     if (a->forced_playouts() || b->forced_playouts())
         return fail(OAMD_INVALID_ARGUMENT, "arena: an engine has forced playouts set (the arena does not use them)");
+    // ... and without exact leaf values
+    if (a->exact_leaves() || b->exact_leaves())
+        return fail(OAMD_INVALID_ARGUMENT, "arena: an engine has exact leaves set (the arena does not use them)");
     return OAMD_OK;
 }
 

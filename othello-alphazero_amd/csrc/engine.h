@@ -94,7 +94,7 @@ struct EngineView {
     float* value;    // G*L
     const float* explore_tab;  // kExploreTab
     float c_base, c_init, eps, alpha;
-    unsigned long long* counters;  // [0..11], tree.hip add_counters / count_launch
+    unsigned long long* counters;  // [0..14], tree.hip add_counters / count_launch, exact_leaves.hip
     int32_t* rowlist;  // G*L: evaluation lists (pipeline group k: from its first game's row)
     int32_t* tstate;   // G*L (entry g*L + t for virtual thread t): batches selected | kTstatePend
     int32_t steps;     // batches per virtual thread and search: ceil(num_simulations / L)
@@ -112,6 +112,12 @@ struct EngineView {
     // from the pruned counts
     float forced_k;
     int32_t prune_targets;
+    // exact leaf values (exact_leaf.h): 0 = off; else a node with
+    // at most exact_empties empties below a root is an exact leaf, and `exact`
+    // holds the per-row flag of the selected leaves (G*L: 0 none, 1 pending,
+    // 2 / 3 / 4 the result), written by the selection and by k_solve_leaves
+    int32_t exact_empties;
+    int32_t* exact;
 };
 
 }  // namespace oamd

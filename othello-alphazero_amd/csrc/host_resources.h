@@ -131,6 +131,7 @@ struct RowBuffers {
     // non-terminal leaves per pipeline group
     DeviceBuf<int32_t> rowlist;
     DeviceBuf<int32_t> tstate;  // per game and virtual thread: batches selected, pending (k_tree)
+    DeviceBuf<int32_t> exact;   // per row: the exact-leaf flag of the selected leaf (engine.h)
 
     // max_depth: path slots per row (engine.h kMaxDepth). A shape that does not
     // fit is allocated whole beside the old set, which is released on success.
@@ -142,8 +143,10 @@ struct RowBuffers {
         if ((rc = t.leaf.alloc(rows)) || (rc = t.depth.alloc(rows)) || (rc = t.trans.alloc(rows)) ||
             (rc = t.path.alloc(rows * max_depth)) || (rc = t.feat.alloc(rows * fw)) ||
             (rc = t.policy.alloc(rows * 65 + kEvalGuard)) || (rc = t.value.alloc(rows + kEvalGuard)) ||
-            (rc = t.flags.alloc(rows)) || (rc = t.rowlist.alloc(rows)) || (rc = t.tstate.alloc(rows)))
+            (rc = t.flags.alloc(rows)) || (rc = t.rowlist.alloc(rows)) || (rc = t.tstate.alloc(rows)) ||
+            (rc = t.exact.alloc(rows)))
             return rc;
+        HIPCHK(hipMemset(t.exact.get(), 0, rows * sizeof(int32_t)));  // no row pending
         HIPCHK(hipMemset(t.policy.get(), 0, rows * 65 * sizeof(float)));
         HIPCHK(hipMemset(t.value.get(), 0, rows * sizeof(float)));
         // guard words behind both (oamd_debug_eval_guards): no launch writes them

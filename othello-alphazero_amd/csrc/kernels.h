@@ -76,6 +76,16 @@ void launch_tree_free(const EngineView& E, hipStream_t s, int g0, int ng, int B,
                       int32_t* finished, float* feat, float* pol, int32_t* remaining, int sim_budget);
 void launch_status(const EngineView& E, int32_t* out, hipStream_t s);
 
+// exact_leaves.hip (exact leaf values): solve every row of
+// [row0, row0 + rows) whose flag E.exact says "pending" and leave the result in
+// the flag; nothing is launched with E.exact_empties == 0. positions: the same
+// solving path over n positions (sign -1 / 0 / +1 for the side to move,
+// OAMD_SOLVE_NONE for a position that is no exact leaf at max_empties; nodes
+// may be null).
+void launch_solve_leaves(const EngineView& E, int row0, int rows, hipStream_t s);
+void launch_solve_positions(const oamd_position* pos, int64_t n, int32_t max_empties, int32_t* sign, int64_t* nodes,
+                            hipStream_t s);
+
 // adjudicate.hip: after the solver ran over the n pending positions (score,
 // flags), write the outcome bits, kFinAdjudicated / kFinSolverFlag and the
 // margin of every slot. accumulate = 0 (self-play): margin[i] is written for

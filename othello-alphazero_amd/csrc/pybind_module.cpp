@@ -193,6 +193,11 @@ struct Engine {
         if (capped)
             throw std::runtime_error("search path exceeded the depth cap (127 plies below the root) in " +
                                      std::to_string(capped) + " game(s)");
+        int64_t faults = 0;
+        check(oamd_engine_exact_leaf_faults(h, &faults));
+        if (faults)
+            throw std::runtime_error(std::to_string(faults) + " row(s) were backed up before their exact leaf was "
+                                     "solved (the solve kernel did not run between a selection and its backup)");
     }
 };
 
@@ -746,6 +751,13 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                  const oamd_forced_playouts f{k, prune_targets ? 1 : 0};
                  check(oamd_engine_set_forced_playouts(e.h, k == 0.0f ? nullptr : &f));
              })
+        // exact leaf values (max_empties 0 = off) and their counters (solves, hits, solver nodes)
+        .def("set_exact_leaves", [](Engine& e, int max_empties) { check(oamd_engine_set_exact_leaves(e.h, max_empties)); })
+        .def("exact_leaf_counters", [](Engine& e) {
+            int64_t solves = 0, hits = 0, nodes = 0;
+            check(oamd_engine_exact_leaf_counters(e.h, &solves, &hits, &nodes));
+            return py::make_tuple(solves, hits, nodes);
+        })
         .def("root_priors",
              [](Engine& e, uintptr_t priors) { check(oamd_engine_root_priors(e.h, reinterpret_cast<float*>(priors))); })
         .def("set_active",
@@ -971,6 +983,23 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
         return bytes;
     });
     // workgroups = 0: the product entry point; >= 1: the experimental one with that grid
+    // exact leaf values: the rule on the host, (sign or OAMD_SOLVE_NONE, nodes), and the device path
+    m.def("_host_exact_leaf", [](int player, uint64_t p1, uint64_t p2, int max_empties) {
+        oamd_position p{};
+        p.player = player;
+        p.player1_discs = p1;
+        p.player2_discs = p2;
+        int32_t sign = 0;
+        int64_t nodes = 0;
+        check(oamd_exact_leaf_sign_nodes(&p, max_empties, &sign, &nodes));
+        return py::make_tuple(sign, nodes);
+    });
+    m.def("_gpu_exact_leaves", [](int device, uintptr_t pos, int64_t n, int max_empties, uintptr_t sign,
+                                  uintptr_t nodes, uintptr_t stream) {
+        check(oamd_exact_leaf_signs(device, reinterpret_cast<const oamd_position*>(pos), n, max_empties,
+                                    reinterpret_cast<int32_t*>(sign), reinterpret_cast<int64_t*>(nodes),
+                                    reinterpret_cast<void*>(stream)));
+    });
     m.def("_gpu_solve", [](int device, uintptr_t pos, int64_t n, int max_empties, int64_t node_limit,
                            uintptr_t move_scores, uintptr_t score, uintptr_t best, uintptr_t flags, uintptr_t nodes,
                            uintptr_t workspace, int workgroups, uintptr_t stream) {

@@ -19,6 +19,7 @@
 
 #include "bitboard.h"
 #include "engine.h"
+#include "exact_leaf.h"
 #include "forced.h"
 #include "kernels.h"
 #include "rng.h"
@@ -289,7 +290,8 @@ __device__ __forceinline__ void select_range(const EngineView& E, int g, GameSta
                                              int hist_n, unsigned long long& sims,
                                              unsigned long long& evals, int* cnt, int list_base,
                                              unsigned long long& depth_sum, int& depth_max,
-                                             unsigned long long& scan_sum, bool fast) {
+                                             unsigned long long& scan_sum, bool fast, unsigned& exact_pending,
+                                             unsigned& exact_hits) {
     const int lane = lane_id();
     const int root = gs->root;
     const uint64_t key = gs->key;
@@ -423,7 +425,19 @@ __device__ __forceinline__ void select_range(const EngineView& E, int g, GameSta
         int* gp = E.path + (size_t)r * kMaxDepth;
         if (lane <= d) gp[lane] = p0;
         if (64 + lane <= d) gp[64 + lane] = p1;
-        const bool valid = lk.player != 0;
+        // exact leaves (exact_leaf.h): a childless node carrying a
+        // mark is a terminal-like leaf: no NN row, meta word 0, no symmetry draw,
+        // not an evaluation. Its row flag tells the solve kernel (pending) and
+        // the backup (the result) what to do. Wave-uniform (lk is). With the
+        // setting off no mark exists, so the test needs no look at
+        // E.exact_empties, and it is written without a branch on purpose: a
+        // loop-invariant branch here makes the compiler clone the selection
+        // loop (152 instead of 48 bytes of scratch per lane in k_tree).
+        int xflag = kExactFlagNone;
+        if (lk.player != 0 && lk.n_children == 0 && exact_mark(lk.first_child)) xflag = exact_flag_of_mark(lk.first_child);
+        exact_pending += xflag == kExactFlagPending ? 1 : 0;
+        exact_hits += xflag > kExactFlagPending ? 1 : 0;
+        const bool valid = lk.player != 0 && xflag == kExactFlagNone;
         int t = 0;
         if (valid) {
             t = draw_transform(key, event);  // search_thread.cpp:92
@@ -433,6 +447,7 @@ __device__ __forceinline__ void select_range(const EngineView& E, int g, GameSta
             E.leaf[r] = node;
             E.depth[r] = d;
             E.trans[r] = t;
+            if (E.exact_empties > 0) E.exact[r] = xflag;
         }
         write_feature_meta(E, r, lk.player, t, valid);
         {
@@ -527,7 +542,7 @@ __device__ __forceinline__ int kth_square(uint64_t mask, int k) {
 // legal_actions order (position.h:308-326), priors policy[transform(a, t)].
 // pol_l: entry `lane` of the leaf's policy row (prefetched by backup_range)
 __device__ __forceinline__ void expand_quads(const EngineView& E, size_t base, int leaf, const Pos& P, int fc,
-                                             int nc, int t, float pol_l) {
+                                             int nc, int t, float pol_l, int child_mark) {
     const int lane = lane_id();
     const int q = lane & 3;
     const int mag = q == 0 ? 1 : (q == 1 ? 7 : (q == 2 ? 8 : 9));
@@ -566,7 +581,8 @@ __device__ __forceinline__ void expand_quads(const EngineView& E, size_t base, i
             c.legal = lg;
             c.next_legal = nx;
             const int id = fc + k;
-            store_link(E.link + base + id, NodeLink{-1, 0, leaf, c.player});
+            // a child with few empties is an exact leaf (pending): never expanded
+            store_link(E.link + base + id, NodeLink{c.player != 0 ? child_mark : kMarkPlain, 0, leaf, c.player});
             store_stat(E.stat + base + id, NodeStat{0, 0.0f, 0.0f, prior});
             store_pos(E.pos + base + id, c);
         }
@@ -597,6 +613,7 @@ __device__ __forceinline__ void backup_range(const EngineView& E, int g, size_t 
         const int d_v = E.depth[rl];
         const int t_v = E.trans[rl];
         const float val_v = E.value[rl];
+        const int ex_v = E.exact_empties > 0 ? E.exact[rl] : kExactFlagNone;  // exact leaves: the row's flag
         const int4 lk_v = *reinterpret_cast<const int4*>(E.link + base + leaf_v);
         const NodePos pos_v = E.pos[base + leaf_v];
         bool expanded_here = false;  // lane j: leaf j of this chunk expanded its node
@@ -631,8 +648,17 @@ __device__ __forceinline__ void backup_range(const EngineView& E, int g, size_t 
                 pol_l = pr[lane];
             }
             const bool already = __ballot(expanded_here && leaf_v == leaf) != 0;
+            // an exact leaf is never expanded: the solve kernel left its result
+            // in the row's flag. A flag still pending means the kernel did not
+            // run or could not take the row: a fault, counted in counter [15]
+            // (check_health raises); the leaf stays pending and backs up a draw
+            const int ex = readlane_i(ex_v, j);
             TS_T(te0);
-            if (lk.player != 0 && lk.n_children == 0 && !already) {
+            if (ex != kExactFlagNone) {
+                if (ex == kExactFlagPending && lane == 0 && E.counters) atomicAdd(E.counters + 15, 1ULL);
+                if (lk.first_child == kMarkPending && ex != kExactFlagPending && lane == 0)
+                    store_link(E.link + base + leaf, NodeLink{exact_mark_of_flag(ex), 0, lk.parent, lk.player});
+            } else if (lk.player != 0 && lk.n_children == 0 && !already) {
                 Pos P;
                 P.player = lk.player;
                 P.pad_ = 0;
@@ -647,11 +673,19 @@ __device__ __forceinline__ void backup_range(const EngineView& E, int g, size_t 
                     const int fc = count;
                     count += nc;
                     ++expansions;
+                    // exact leaves (exact_leaf.h): every child of a move has one
+                    // empty fewer than P, the child of a pass as many: one
+                    // wave-uniform test per expansion gives the children's mark
+                    const int child_mark =
+                        E.exact_empties > 0 && popcount64(~(P.p1 | P.p2)) - (P.legal ? 1 : 0) <= E.exact_empties
+                            ? kMarkPending
+                            : kMarkPlain;
                     if (P.legal) {
-                        expand_quads(E, base, leaf, P, fc, nc, t, polj);
+                        expand_quads(E, base, leaf, P, fc, nc, t, polj, child_mark);
                     } else if (lane == 0) {  // the pass: one child (position.h:382-386)
                         const Pos c = apply_action(P, 64);
-                        store_link(E.link + base + fc, NodeLink{-1, 0, leaf, c.player});
+                        store_link(E.link + base + fc,
+                                   NodeLink{c.player != 0 ? child_mark : kMarkPlain, 0, leaf, c.player});
                         store_stat(E.stat + base + fc, NodeStat{0, 0.0f, 0.0f, E.policy[(size_t)r * 65 + 64]});
                         store_pos(E.pos + base + fc, c);
                     }
@@ -663,7 +697,9 @@ __device__ __forceinline__ void backup_range(const EngineView& E, int g, size_t 
             TS_ADD(kTsExpand, te1 - te0);
             if (d > 0) {
                 float v;
-                if (lk.player != 0) {
+                if (ex != kExactFlagNone) {
+                    v = exact_parent_value(ex == kExactFlagPending ? 0 : exact_sign_of_flag(ex));
+                } else if (lk.player != 0) {
                     v = -readlane_f(val_v, j);
                 } else {
                     // terminal: score from the perspective of the parent's player
@@ -744,6 +780,8 @@ struct RoundAcc {
     unsigned long long scan_sum = 0;  // children scanned over every descent level
     int depth_max = 0;
     unsigned expansions = 0;          // leaves expanded (children = the node count's growth)
+    unsigned exact_pending = 0;       // exact leaves selected while pending
+    unsigned exact_hits = 0;          // ... and while solved
 };
 
 // Playout cap randomization: the batches per virtual thread
@@ -807,14 +845,18 @@ __device__ __forceinline__ bool search_round(const EngineView& E, int g, GameSta
                 over = true;  // no cut left: the chain runs on in this round
             }
             const unsigned long long ev0 = acc.evals;
+            const unsigned xp0 = acc.exact_pending;
             TS_T(tsel0);
             select_range(E, g, gs, base, t * B, (t + 1) * B, event, hist_node, hist_n, acc.sims, acc.evals, cnt_add,
-                         list_base, acc.depth_sum, acc.depth_max, acc.scan_sum, fast);
+                         list_base, acc.depth_sum, acc.depth_max, acc.scan_sum, fast, acc.exact_pending,
+                         acc.exact_hits);
             TS_T(tsel1);
             TS_ADD(kTsSelect, tsel1 - tsel0);
             TS_ADD(kTsBatches, 1);
             ++sel;
-            if (acc.evals != ev0 || !E.terminal_skip) {
+            // the round trip: an NN row, or a pending exact leaf for the solve
+            // kernel; terminal and solved leaves alone are "all terminal"
+            if (acc.evals != ev0 || acc.exact_pending != xp0 || !E.terminal_skip) {
                 pend = true;
             } else {
                 backup_range(E, g, base, t * B, (t + 1) * B, count, overflow, acc.expansions);
@@ -863,6 +905,7 @@ __device__ __forceinline__ void add_counters(const EngineView& E, const RoundAcc
         atomicAdd(E.counters + 9, (unsigned long long)acc.expansions);
         atomicAdd(E.counters + 10, (unsigned long long)children);
     }
+    if (acc.exact_hits) atomicAdd(E.counters + 13, (unsigned long long)acc.exact_hits);
 }
 
 // counter [11]: one per tree launch (lane 0 of its first wave, before any
@@ -902,6 +945,7 @@ __device__ __forceinline__ void tree_round_kernel(const EngineView& E, int g0, i
                     E.leaf[r] = -1;
                     E.depth[r] = 0;
                     E.trans[r] = 0;
+                    if (E.exact_empties > 0) E.exact[r] = kExactFlagNone;
                 }
                 write_feature_meta(E, r, 1, 0, false);
             }
@@ -1069,6 +1113,13 @@ __device__ void move_root(const EngineView& E, int g, int action) {
     } else {
         const uint64_t legal = E.pos[base + root].legal;
         next = lk.first_child + child_index_of(legal, lk.n_children, action);
+        // the root is never an exact leaf: a pending or solved mark goes, and
+        // the node is an ordinary unexpanded leaf again
+        if (E.exact_empties > 0) {
+            const NodeLink nl = load_link(E.link + base + next);
+            if (nl.n_children == 0 && exact_mark(nl.first_child))
+                store_link(E.link + base + next, NodeLink{kMarkPlain, 0, nl.parent, nl.player});
+        }
     }
     for (int k = 15; k > 0; --k) gs->hist[k] = gs->hist[k - 1];
     gs->hist[0] = root;

@@ -24,7 +24,9 @@ playout cap randomization (full searches recorded, fast ones only played:
 gives every game of a free-running call a work budget instead of a move count.
 ``BatchedMCTS.set_forced_playouts`` switches on forced playouts at the root of
 full searches and policy target pruning (``prune_visit_counts`` is the pruning
-rule on the host).
+rule on the host). ``BatchedMCTS.set_exact_leaves`` makes the search solve
+leaves with few empties instead of asking the net (``exact_leaf_value`` is the
+rule on the host, ``exact_leaf_values`` the solve kernel's path on the GPU).
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -52,6 +54,7 @@ from .selfplay import FIN_FAST, SelfPlayCollector, self_play  # noqa: E402,F401
 from .replay import ReplayBuffer  # noqa: E402,F401
 from .endgame import EndgameSolution, endgame_move_loss, solve_endgames, solve_position  # noqa: E402,F401
 from .adjudication import adjudicate  # noqa: E402,F401
+from .exact_leaves import exact_leaf_value, exact_leaf_values  # noqa: E402,F401
 from .training import (  # noqa: E402,F401
     SampleBuffer,
     alphazero_loss,
@@ -88,4 +91,6 @@ __all__ = [
     "FIN_FAST",
     "playout_cap_is_full",
     "prune_visit_counts",
+    "exact_leaf_value",
+    "exact_leaf_values",
 ]

@@ -135,6 +135,7 @@ class Arena:
         if mcts_a is mcts_b:
             raise ValueError("Arena needs two different engines (one tree per player)")
         self.a, self.b = mcts_a, mcts_b
+        self._reject_exact_leaves()
         self.num_games = mcts_a.num_games
         self.device = mcts_a.device
         G = self.num_games
@@ -158,7 +159,16 @@ class Arena:
         arena.seed = seed
         return arena
 
+    def _reject_exact_leaves(self) -> None:
+        """Matches are played by the plain search: an engine with exact leaf
+        values set (BatchedMCTS.set_exact_leaves) is rejected, as
+        the C layer rejects it (and a playout cap, and forced playouts)."""
+        for name, m in (("A", self.a), ("B", self.b)):
+            if getattr(m, "exact_leaves", 0):
+                raise ValueError(f"arena: engine {name} has exact leaves set (the arena does not use them)")
+
     def _streams(self) -> None:
+        self._reject_exact_leaves()
         self.a._stream()
         self.b._stream()
 

@@ -16,6 +16,7 @@ import torch
 
 from ._othello_mcts_impl import SearchConfig, _Engine
 from .adjudication import check_adjudicate_empties
+from .exact_leaves import check_exact_empties
 from .native import NativeNet, resolve
 
 
@@ -66,6 +67,7 @@ class BatchedMCTS:
         self._targets_p = None
         self._margin = None
         self._C = C
+        self.exact_leaves = 0  # set_exact_leaves
 
     @property
     def rows_per_step(self) -> int:
@@ -180,6 +182,33 @@ class BatchedMCTS:
         if not (math.isfinite(kf) and kf > 0.0):
             raise ValueError(f"Expected a finite forced playout factor k > 0, but got {k}.")
         self.engine.set_forced_playouts(kf, bool(prune_targets))
+
+    def set_exact_leaves(self, max_empties: int | None = None) -> None:
+        """Exact leaf values. With ``max_empties = E`` in 1..10 a
+        search never expands and never evaluates a node below the root that is
+        not terminal and has at most E empties: the first visit solves it with
+        the exact endgame solver, and every visit backs up the sign of the exact
+        result as a terminal leaf would (no NN row, no random event, not an
+        evaluation). The root itself is always evaluated and expanded. The
+        external-evaluator path, ``search`` with a native net, ``selfplay_steps``
+        and every schedule follow the same rule and give the same trees.
+        ``None`` (or 0): off, the default. The value may change only while no
+        game holds a tree built under another value: before the first search,
+        or after ``reset()`` of all games or ``random_openings`` (ValueError
+        otherwise). Independent of the playout cap, forced playouts and
+        ``adjudicate_empties``. The arena rejects an engine that has it."""
+        e = 0 if max_empties is None else check_exact_empties(max_empties, allow_off=True)
+        self.engine.set_exact_leaves(e)
+        self.exact_leaves = e
+
+    def exact_leaf_counters(self) -> dict[str, int]:
+        """Since the engine was created (waits for the engine's stream):
+        ``solves`` rows that ended at an exact leaf not solved yet (each one is
+        solved), ``hits`` rows that ended at a solved leaf, ``nodes`` positions
+        the solves visited."""
+        self._stream()
+        solves, hits, nodes = self.engine.exact_leaf_counters()
+        return {"solves": solves, "hits": hits, "nodes": nodes}
 
     def root_priors(self) -> torch.Tensor:
         """Stored priors of every game's root children, (G, 65) indexed by action

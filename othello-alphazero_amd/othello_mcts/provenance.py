@@ -18,9 +18,9 @@ INCLUDE = Path(__file__).resolve().parent.parent.parent / "include"
 # the sources each kernel family is compiled from
 FAMILIES = {
     "resnet": ["resnet.hip", "kernels.h"],
-    "tree": ["tree.hip", "engine.h", "bitboard.h", "rng.h", "forced.h", "kernels.h"],
+    "tree": ["tree.hip", "engine.h", "bitboard.h", "rng.h", "forced.h", "exact_leaf.h", "solver.h", "kernels.h"],
     "all": ["adjudicate.hip", "bitboard.h", "capi.hip", "capi_data.hip", "capi_internal.h", "capi_net.hip", "capi_play.hip",
-            "capi_version.hip", "engine.h", "forced.h", "host_resources.h", "kernels.h", "replay.h", "replay.hip", "resnet.hip", "rng.h",
+            "capi_version.hip", "engine.h", "exact_leaf.h", "exact_leaves.hip", "forced.h", "host_resources.h", "kernels.h", "replay.h", "replay.hip", "resnet.hip", "rng.h",
             "schedule.h", "solver.h", "solver.hip", "timing.h", "tree.hip",
             "../../include/othello_mcts_amd.h", "../../include/othello_mcts_amd_experimental.h"],
 }

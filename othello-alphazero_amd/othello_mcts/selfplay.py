@@ -125,7 +125,8 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
               opening_moves: int = 0, device: str | torch.device = "cpu",
               moves_per_call: int = 16, adjudicate_empties: int = 0,
               split: bool = False, playout_cap: tuple[float, int] | None = None,
-              sim_budget: int = 0, forced_playouts: float | None = None) -> dict[str, list[torch.Tensor]]:
+              sim_budget: int = 0, forced_playouts: float | None = None,
+              exact_leaves: int | None = None) -> dict[str, list[torch.Tensor]]:
     """Play until at least ``games`` games have completed across the batch (each
     slot restarts when its game ends) and return their samples in the
     reference's ``_self_play`` format (train.py:404-452). ``opening_moves=0``
@@ -158,7 +159,12 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
     forced_playouts = k: sets the engine's forced playouts with policy target
     pruning for this run (``BatchedMCTS.set_forced_playouts(k)``, DESIGN.md §18;
     None leaves the engine as it is). The policy samples are then the pruned
-    targets; nothing else about the samples changes."""
+    targets; nothing else about the samples changes.
+
+    exact_leaves = E: sets the engine's exact leaf values for this run
+    (``BatchedMCTS.set_exact_leaves(E)``; None leaves the engine
+    as it is). The engine must hold no tree built under another value (a fresh
+    engine, or one whose games were all reset)."""
     from .adjudication import check_adjudicate_empties
     from .native import resolve
 
@@ -167,6 +173,8 @@ def self_play(batched, neural_net, games: int, temperature_moves: int = 12, temp
         batched.set_playout_cap(*playout_cap)
     if forced_playouts is not None:
         batched.set_forced_playouts(forced_playouts)
+    if exact_leaves is not None:
+        batched.set_exact_leaves(exact_leaves)
     sim_budget = int(sim_budget)
     if sim_budget < 0:
         raise ValueError(f"Expected sim_budget >= 0, but got {sim_budget}.")

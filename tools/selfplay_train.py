@@ -13,7 +13,7 @@ descend deeper than those of any random init). Output: the trained state_dict
 as float16 (npz, the reference's keys) + a JSON log of the iterations.
 
 Usage (GPU box): python tools/selfplay_train.py OUT_PREFIX [iterations] [games] [seconds]
-                 [packed [exact=K]] [adjudicate=K] [split] [cap=P:N] [budget=S] [forced=K]
+                 [packed [exact=K]] [adjudicate=K] [split] [cap=P:N] [budget=S] [forced=K] [exact_leaves=E]
 
 packed: keep the samples in the packed ReplayBuffer (500,000 positions = 4
 million samples in 0.2 GB, one add per selfplay_steps call, no host wait in the
@@ -44,6 +44,8 @@ call gives each game S nominal simulations instead of 16 moves
 
 forced=K: forced playouts at the root of full searches with factor K and policy
 target pruning (BatchedMCTS.set_forced_playouts(K); KataGo: 2).
+exact_leaves=E: the search solves leaves with at most E empties (1..10) instead
+of asking the net (BatchedMCTS.set_exact_leaves(E)).
 
 new_positions (packed) is the ring head's advance, valid while one iteration
 stores fewer positions than the ring holds; new_games / selfplay_s and
@@ -127,6 +129,8 @@ def main():
     budget = budget[0] if budget else 0
     forced = [float(w[7:]) for w in sys.argv[5:] if w.startswith("forced=")]
     forced = forced[0] if forced else None
+    exact_leaves = [int(w[13:]) for w in sys.argv[5:] if w.startswith("exact_leaves=")]
+    exact_leaves = exact_leaves[0] if exact_leaves else 0
     L = 2 * 16
     nominal_min = -(-(cap[1] if cap else 800) // L) * L  # the smallest search's nominal simulations
     slots = min(64, -(-budget // nominal_min)) if budget else 16
@@ -145,6 +149,8 @@ def main():
         b.set_playout_cap(*cap)
     if forced:
         b.set_forced_playouts(forced)
+    if exact_leaves:
+        b.set_exact_leaves(exact_leaves)  # right after the reset: no tree built yet
     if packed:
         buf = om.ReplayBuffer(G, 8, capacity=500_000, device=dev, track_exact=bool(exact))
     else:
@@ -217,7 +223,7 @@ def main():
                                                     "exact_split": split and bool(exact),
                                                     "adjudicate_empties": K, "adjudicate_split": split and K > 0,
                                                     "playout_cap": cap, "sim_budget": budget, "slots_per_call": slots,
-                                                    "forced_playouts": forced},
+                                                    "forced_playouts": forced, "exact_leaves": exact_leaves},
                                                    indent=1))
 
 
