@@ -690,7 +690,7 @@ int orc_mcts_node_count(const orc_mcts *m) { return m->count; }
 uint64_t orc_mcts_events(const orc_mcts *m) { return m->event; }
 
 /* The self-play move choice of train.py:421-430 as the on-device driver
- * (tree.hip k_selfplay_move) draws it from one event of the game's stream:
+ * (selfplay.hip k_selfplay_move) draws it from one event of the game's stream:
  * for ply < temperature_moves sample a child with p ~ N^(1/temperature) by a
  * sequential float cdf (numpy.random.choice's rule); afterwards argmax of N
  * with a uniform random tie-break; an unexpanded root picks a legal action

@@ -1,7 +1,8 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
-  liboamd.so               HIP kernels (tree.hip, resnet.hip, replay.hip, solver.hip, adjudicate.hip,
-                           exact_leaves.hip) + the C ABI
+  liboamd.so               HIP kernels (tree.hip, selfplay.hip, arena.hip over the headers wave.h, tree_search.h,
+                           tree_game.h; resnet.hip, replay.hip, solver.hip, adjudicate.hip, exact_leaves.hip)
+                           + the C ABI
                            (capi.hip and, by subsystem, capi_net.hip, capi_play.hip, capi_data.hip; capi_version.hip
                            carries the source hashes), hipcc --offload-arch=gfx950
   _othello_mcts_impl*.so   pybind11 host layer (pybind_module.cpp) over the C ABI
@@ -30,18 +31,20 @@ ARCH = os.environ.get("OAMD_ARCH", "gfx950")
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", str(CSRC), "-I", str(INCLUDE),
           "-Wall", "-Wno-unused-function", "-fno-gpu-rdc", *os.environ.get("OAMD_EXTRA_FLAGS", "").split()]
-# tree.hip / rng.h, capi.hip's tables and capi_net.hip's weight fold must
+# the tree units (TREE_UNITS) / rng.h, capi.hip's tables and capi_net.hip's weight fold must
 # reproduce the reference's float arithmetic bit for bit: no FMA contraction,
 # IEEE division and sqrt. The C ABI's other host units share inline host code
 # with those two (capi_internal.h), so they are built the same way.
 EXACT = ["-ffp-contract=off", "-fno-fast-math"]
-# tree.hip's kernels read statistics, links and game state that the same wave
-# has just written with vector stores (ordered by a wavefront fence, tree.hip
+# the tree kernels read statistics, links and game state that the same wave
+# has just written with vector stores (ordered by a wavefront fence, wave.h
 # wave_order): no global load may go through the scalar cache, which does not
 # see those stores (tests/test_cpu_host.py checks the ISA)
 NO_SCALAR_LOADS = ["-mllvm", "-amdgpu-scalarize-global-loads=false"]
+# every unit that includes tree_search.h or tree_game.h is built this way
+TREE_UNITS = ("tree.hip", "selfplay.hip", "arena.hip")
 UNITS = {
-    "tree.hip": EXACT + NO_SCALAR_LOADS,
+    **{u: EXACT + NO_SCALAR_LOADS for u in TREE_UNITS},
     "capi.hip": EXACT,
     "capi_net.hip": EXACT,
     "capi_play.hip": EXACT,

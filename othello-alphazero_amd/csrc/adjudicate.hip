@@ -1,7 +1,7 @@
 // Adjudication by the exact solver: the apply step.
 //
-// The self-play driver and the arena (tree.hip selfplay_move_game,
-// k_arena_move) end a game whose searched move left a non-terminal root with
+// The self-play driver and the arena (tree_game.h selfplay_move_game,
+// arena.hip k_arena_move) end a game whose searched move left a non-terminal root with
 // at most K empties and put that root into the pending slot of the move's
 // `finished` word; a game that ended on the board leaves its final position
 // there with player 0. Slots of moves that ended nothing stay all-zero (the

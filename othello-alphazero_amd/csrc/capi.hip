@@ -2,7 +2,7 @@
 // configuration with the reference's exception messages, the step API, the
 // queries, and every native search schedule. The net is in capi_net.hip, the
 // self-play move, adjudication and the arena in capi_play.hip, the replay ring
-// and the endgame solver in capi_data.hip. All compute is in tree.hip /
+// and the endgame solver in capi_data.hip. All compute is in tree.hip, selfplay.hip, arena.hip /
 // resnet.hip.
 
 #include <cmath>
@@ -1033,7 +1033,7 @@ int oamd_engine_set_forced_playouts(oamd_engine* e, const oamd_forced_playouts* 
     return OAMD_OK;
 }
 
-// The rule of tree.hip root_target_count on the host: the same forced.h code,
+// The rule of tree_game.h root_target_count on the host: the same forced.h code,
 // the exploration rate as build_tables computes it.
 int oamd_prune_visit_counts(int32_t n_children, int32_t root_visit_count, const int32_t* visits, const float* q,
                             const float* priors, float c_puct_base, float c_puct_init, float k, int32_t* pruned_out) {

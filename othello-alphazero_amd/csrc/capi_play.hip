@@ -24,7 +24,7 @@ SelfplayParams oamd::selfplay_params(const oamd_selfplay_config* cfg) {
 // ---------------------------------------------------------------------------
 // Adjudication by the exact solver. A call zeroes its pending
 // slots on the caller's stream before the moves (adjudicate_begin), the move
-// kernels mark them (tree.hip), and the resolve step, on the caller's stream
+// kernels mark them (tree_game.h end_of_game), and the resolve step, on the caller's stream
 // after every group has joined, solves them and writes the outcome bits and
 // the margins (adjudicate.hip). Everything is enqueued only.
 // ---------------------------------------------------------------------------
@@ -127,7 +127,7 @@ int oamd_engine_random_openings(oamd_engine* e, int32_t max_moves, uint64_t seed
 }
 
 // ---------------------------------------------------------------------------
-// Arena: G matches between two engines (tree.hip k_arena_begin / k_arena_move)
+// Arena: G matches between two engines (arena.hip k_arena_begin / k_arena_move)
 // ---------------------------------------------------------------------------
 static int arena_checks(const oamd_engine* a, const oamd_engine* b) {
     if (!a || !b || a == b) return fail(OAMD_INVALID_ARGUMENT, "arena: expected two different engines");

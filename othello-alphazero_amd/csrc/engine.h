@@ -56,7 +56,7 @@ struct GameState {
 static_assert(sizeof(GameState) == 128, "GameState layout");
 
 // Arena status bits reported in `finished` beside the outcome (bits 0-1) and
-// the self-play driver's bits 2-3 (tree.hip k_arena_move)
+// the self-play driver's bits 2-3 (arena.hip k_arena_move)
 constexpr int32_t kArenaDesync = 16;
 // ... and of every adjudicating driver: the game was ended at
 // this move by the exact solver (in GameState::arena: the match is over); the
@@ -94,7 +94,7 @@ struct EngineView {
     float* value;    // G*L
     const float* explore_tab;  // kExploreTab
     float c_base, c_init, eps, alpha;
-    unsigned long long* counters;  // [0..14], tree.hip add_counters / count_launch, exact_leaves.hip
+    unsigned long long* counters;  // [0..14], tree_search.h add_counters / count_launch, exact_leaves.hip
     int32_t* rowlist;  // G*L: evaluation lists (pipeline group k: from its first game's row)
     int32_t* tstate;   // G*L (entry g*L + t for virtual thread t): batches selected | kTstatePend
     int32_t steps;     // batches per virtual thread and search: ceil(num_simulations / L)

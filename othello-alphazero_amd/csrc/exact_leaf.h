@@ -1,4 +1,4 @@
-// Exact leaf values: the rule, once, for the device (tree.hip,
+// Exact leaf values: the rule, once, for the device (tree_search.h,
 // exact_leaves.hip) and the host (oamd_exact_leaf_sign). A node with at most E
 // empties that is not terminal and not a game's root is never expanded and
 // never evaluated by the net: it is solved once (solver.h) and every later

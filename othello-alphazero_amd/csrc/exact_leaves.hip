@@ -1,5 +1,5 @@
 // Exact leaf values on the device (the rule is exact_leaf.h, the
-// search's side of it tree.hip).
+// search's side of it tree_search.h).
 //
 //   k_solve_leaves     over the rows of a pipeline group (or all rows, the step
 //                      API), between a round's tree launch and the next one. A

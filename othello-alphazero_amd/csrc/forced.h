@@ -1,5 +1,5 @@
 // Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2;
-// DESIGN.md §18): the rule, once, for the device (tree.hip select_range and
+// DESIGN.md §18): the rule, once, for the device (tree_search.h select_range and
 // write_targets) and the host (oamd_prune_visit_counts). All arithmetic is
 // fp32 in exactly the order written; both sides are built without contraction
 // and with IEEE division and square root, so they agree bit for bit.

@@ -127,7 +127,7 @@ struct RowBuffers {
     DeviceBuf<uint64_t> feat;
     DeviceBuf<float> policy, value;
     DeviceBuf<uint8_t> flags;
-    // evaluation lists of the native search (tree.hip append_rows): the rows of
+    // evaluation lists of the native search (tree_search.h append_rows): the rows of
     // non-terminal leaves per pipeline group
     DeviceBuf<int32_t> rowlist;
     DeviceBuf<int32_t> tstate;  // per game and virtual thread: batches selected, pending (k_tree)

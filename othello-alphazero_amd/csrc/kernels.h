@@ -25,7 +25,11 @@ struct SelfplayParams {
     oamd_position* adj_pending = nullptr;
 };
 
-// tree.hip
+// blocks of b threads that cover n items
+static inline unsigned blocks_for(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+// tree.hip: the round kernels, the step API, game state and root read-outs,
+// batched bitboards
 // One search round for games [g0, g0 + ng) (ng < 0: to the end): for each
 // virtual thread t in [t0, t1) (t1 < 0: T), back up its previous batch
 // (do_backup), then select its next B leaves (do_select). T * B must equal
@@ -37,6 +41,17 @@ void launch_tree(const EngineView& E, hipStream_t s, bool do_backup, bool do_sel
                  int g0 = 0, int ng = -1, int t0 = 0, int t1 = -1, int* cnt_add = nullptr,
                  int* cnt_reset = nullptr, bool fresh = false, int budget = 0, int max_cuts = 0,
                  bool timed = false, int* cuts_out = nullptr);
+// Free-running self-play (k_tree_free): begin sets every game of the
+// group to play n_moves moves starting with a fresh search and counts them in
+// *remaining; each round runs one search round per game, a game's move in the
+// round its search completes, and its next search's first round after it.
+// *remaining must be zeroed before begin (stream order). sim_budget > 0 (with
+// per_move): the work budget of k_free_begin's comment, n_moves = the slices.
+void launch_free_begin(const EngineView& E, int g0, int ng, int n_moves, int32_t* remaining, int32_t* actions,
+                       int32_t* finished, int per_move, int sim_budget, hipStream_t s);
+void launch_tree_free(const EngineView& E, hipStream_t s, int g0, int ng, int B, int* cnt_add, int* cnt_reset,
+                      int budget, bool timed, const SelfplayParams& sp, int n_moves, int per_move, int32_t* actions,
+                      int32_t* finished, float* feat, float* pol, int32_t* remaining, int sim_budget);
 void launch_features_f32(const EngineView& E, float* out, int row_begin, int rows, hipStream_t s);
 void launch_set_evaluation(const EngineView& E, const float* pol, const float* val, int row_begin,
                            int rows, hipStream_t s);
@@ -49,12 +64,17 @@ void launch_root_stats(const EngineView& E, int game_begin, int n_games, oamd_ro
 // (G, 65) stored priors of the root children by action, 0 where not a child
 void launch_root_priors(const EngineView& E, float* priors, hipStream_t s);
 void launch_self_play_data(const EngineView& E, int g, float* feat, float* pol, hipStream_t s);
-void launch_selfplay_move(const EngineView& E, const SelfplayParams& sp, int g0, int ng, int32_t* actions,
-                          int32_t* finished, float* feat, float* pol, hipStream_t s);
-void launch_random_openings(const EngineView& E, int max_moves, uint64_t seed, hipStream_t s);
 // Per-game search mask (active: G bytes on the device, nullptr = every game)
 void launch_set_active(const EngineView& E, const uint8_t* active, hipStream_t s);
-// Arena (tree.hip k_arena_begin / k_arena_move): match g = game g of engines A
+void launch_status(const EngineView& E, int32_t* out, hipStream_t s);
+void launch_legal_moves(const uint64_t* me, const uint64_t* opp, uint64_t* out, int64_t n,
+                        hipStream_t s);
+void launch_flips(const uint64_t* mv, const uint64_t* me, const uint64_t* opp, uint64_t* out,
+                  int64_t n, hipStream_t s);
+void launch_apply_positions(const Pos* in, const int32_t* actions, Pos* out, int64_t n,
+                            hipStream_t s);
+
+// arena.hip (k_arena_begin / k_arena_move): match g = game g of engines A
 // and B (same G). begin resets both games, plays the opening plies in both
 // trees and activates the side to move; move plays one ply of every match;
 // count adds the matches still running to *remaining (zeroed by the caller).
@@ -63,18 +83,11 @@ void launch_arena_begin(const EngineView& EA, const EngineView& EB, uint64_t see
 void launch_arena_count(const EngineView& EA, int32_t* remaining, hipStream_t s);
 void launch_arena_move(const EngineView& EA, const EngineView& EB, const SelfplayParams& sp, int32_t* actions,
                        int32_t* finished, int32_t* discs, int32_t* remaining, hipStream_t s);
-// Free-running self-play (tree.hip k_tree_free): begin sets every game of the
-// group to play n_moves moves starting with a fresh search and counts them in
-// *remaining; each round runs one search round per game, a game's move in the
-// round its search completes, and its next search's first round after it.
-// *remaining must be zeroed before begin (stream order). sim_budget > 0 (with
-// per_move): the work budget of k_free_begin's comment, n_moves = the slices.
-void launch_free_begin(const EngineView& E, int g0, int ng, int n_moves, int32_t* remaining, int32_t* actions,
-                       int32_t* finished, int per_move, int sim_budget, hipStream_t s);
-void launch_tree_free(const EngineView& E, hipStream_t s, int g0, int ng, int B, int* cnt_add, int* cnt_reset,
-                      int budget, bool timed, const SelfplayParams& sp, int n_moves, int per_move, int32_t* actions,
-                      int32_t* finished, float* feat, float* pol, int32_t* remaining, int sim_budget);
-void launch_status(const EngineView& E, int32_t* out, hipStream_t s);
+
+// selfplay.hip: random openings and the self-play move of searched games
+void launch_selfplay_move(const EngineView& E, const SelfplayParams& sp, int g0, int ng, int32_t* actions,
+                          int32_t* finished, float* feat, float* pol, hipStream_t s);
+void launch_random_openings(const EngineView& E, int max_moves, uint64_t seed, hipStream_t s);
 
 // exact_leaves.hip (exact leaf values): solve every row of
 // [row0, row0 + rows) whose flag E.exact says "pending" and leave the result in
@@ -93,12 +106,6 @@ void launch_solve_positions(const oamd_position* pos, int64_t n, int32_t max_emp
 // slots of matches that ended are touched.
 void launch_adjudicate_apply(const oamd_position* pending, const int32_t* score, const int32_t* flags, int64_t n,
                              int32_t* finished, int32_t* margin, int accumulate, hipStream_t s);
-void launch_legal_moves(const uint64_t* me, const uint64_t* opp, uint64_t* out, int64_t n,
-                        hipStream_t s);
-void launch_flips(const uint64_t* mv, const uint64_t* me, const uint64_t* opp, uint64_t* out,
-                  int64_t n, hipStream_t s);
-void launch_apply_positions(const Pos* in, const int32_t* actions, Pos* out, int64_t n,
-                            hipStream_t s);
 
 // resnet.hip
 struct NetView {

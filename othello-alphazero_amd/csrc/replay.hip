@@ -39,7 +39,7 @@ constexpr int kCommitThreads = 1024;
 constexpr int kCommitWaves = kCommitThreads / 64;
 constexpr int kGatherWaves = 4;
 
-// finished word of the self-play driver (tree.hip selfplay_move_game)
+// finished word of the self-play driver (tree_game.h selfplay_move_game)
 constexpr int kFinOutcome = 3, kFinNoTargets = 4, kFinOverflow = 8, kFinSolverFlag = 64, kFinFast = 128;
 
 __device__ __forceinline__ void raise_flag(int64_t* counters, int bit) {

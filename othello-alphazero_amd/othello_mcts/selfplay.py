@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-# BatchedMCTS.selfplay_move "finished" codes (csrc/tree.hip k_selfplay_move):
+# BatchedMCTS.selfplay_move "finished" codes (csrc/selfplay.hip k_selfplay_move):
 # bits 0-1 outcome of a game that ended with this move, bit 2 no targets were
 # written (unexpanded root), bit 3 the game's node pool overflowed
 FIN_NONE, FIN_DRAW, FIN_BLACK, FIN_WHITE = 0, 1, 2, 3

@@ -18,7 +18,7 @@ Search: H = 8, T = 1 x B = 16, 800 simulations (50 batches), eps = 0
 (no Dirichlet noise), c_base 20000, c_init 2.5. With eps = 0 and T = 1 a
 search is a deterministic function of (position with its history, net, game
 key). The key of game g under engine seed s is the engine's
-(csrc/tree.hip reset: mix64(s ^ mix64(g + 0x632BE59BD9B4E019))); the GPU test
+(csrc/tree_game.h init_game: mix64(s ^ mix64(g + 0x632BE59BD9B4E019))); the GPU test
 asserts the engine reports the same keys.
 
 Positions: N games from the initial position, each played k = 12..40 plies by
@@ -76,7 +76,7 @@ M64 = (1 << 64) - 1
 
 
 def game_key(seed: int, g: int) -> int:
-    """csrc/tree.hip reset: gs->key = mix64(seed ^ mix64(g + 0x632BE59BD9B4E019))."""
+    """csrc/tree_game.h init_game: gs->key = mix64(seed ^ mix64(g + 0x632BE59BD9B4E019))."""
     lib = O.lib()
     return lib.orc_mix64((seed ^ lib.orc_mix64((g + 0x632BE59BD9B4E019) & M64)) & M64)
 

@@ -1,4 +1,4 @@
-"""The search's bit-packed feature rows (csrc/tree.hip write_feature_meta /
+"""The search's bit-packed feature rows (csrc/tree_search.h write_feature_meta /
 flush_ancestors), written and read back in numpy: what the packed prologue of
 the fused ResNet (csrc/resnet.hip, IN == kPacked) decodes.
 

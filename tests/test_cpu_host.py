@@ -58,6 +58,41 @@ def test_loaded_library_was_built_from_the_sources_on_disk():
     assert lib.oamd_source_hash(b"nope") is None
 
 
+def test_provenance_families_list_every_source():
+    """The hashed file lists of provenance.FAMILIES are kept by hand: "all"
+    must hold every .hip and .h of csrc/, and "tree" every project header its
+    units include, directly or through another header (found by scanning
+    #include "..."), so that moving code into a new file cannot silently drop
+    it from the hash."""
+    import os
+
+    from othello_mcts import provenance
+
+    csrc = provenance.CSRC
+    on_disk = {p.name for p in csrc.iterdir() if p.suffix in (".hip", ".h")}
+    assert on_disk <= set(provenance.FAMILIES["all"]), sorted(on_disk - set(provenance.FAMILIES["all"]))
+    for names in provenance.FAMILIES.values():
+        assert len(set(names)) == len(names)
+        assert all((csrc / n).is_file() for n in names)
+
+    def included(name, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', (csrc / name).read_text(), re.M):
+            rel = os.path.relpath(os.path.normpath(csrc / os.path.dirname(name) / inc), csrc).replace(os.sep, "/")
+            if rel not in seen:
+                seen.add(rel)
+                included(rel, seen)
+        return seen
+
+    tree = provenance.FAMILIES["tree"]
+    units = [n for n in tree if n.endswith(".hip")]
+    assert {"tree.hip", "selfplay.hip", "arena.hip"} <= set(units)
+    headers = set()
+    for u in units:
+        included(u, headers)
+    assert {"wave.h", "tree_search.h", "tree_game.h"} <= headers
+    assert headers <= set(tree), sorted(headers - set(tree))
+
+
 def test_abi_device_count_without_gpu_is_safe():
     lib = ctypes.CDLL(str(PKG / "othello_mcts" / "liboamd.so"))
     n = ctypes.c_int32(-1)
@@ -360,13 +395,15 @@ def test_type_stub_covers_the_reference_surface_and_the_module():
 
 def test_k_tree_reads_no_written_state_through_the_scalar_cache(tmp_path):
     """k_tree orders each leaf's statistic stores before the next
-    descent's loads with a wavefront fence, not a vmcnt(0) drain (tree.hip
+    descent's loads with a wavefront fence, not a vmcnt(0) drain (wave.h
     wave_order). That holds for VECTOR loads (a wave's vector memory
     operations reach the cache in order); a load the compiler turned into a
     scalar s_load would go through the scalar cache, which does not see the
-    wave's vector stores. build.py compiles tree.hip with
+    wave's vector stores. build.py compiles every unit that includes the
+    shared search headers (tree_search.h, tree_game.h) with
     -amdgpu-scalarize-global-loads=false, so no global load is scalarised;
-    the gfx950 ISA of the built kernels confirms it: every s_load of k_tree
+    the gfx950 ISA of the built kernels, in whichever of those units' objects
+    holds them, confirms it: every s_load of k_tree
     (and of its uncapped twin k_tree_wide)
     reads the kernel arguments (one base register, offsets inside the
     argument segment), and every s_load of k_tree_free (which reloads its
@@ -377,34 +414,40 @@ def test_k_tree_reads_no_written_state_through_the_scalar_cache(tmp_path):
     spec = importlib.util.spec_from_file_location("oamd_build", PKG / "build.py")
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    assert "-amdgpu-scalarize-global-loads=false" in b.UNITS["tree.hip"]
+    shared = re.compile(r'#include "(tree_search|tree_game)\.h"')
+    units = [u for u in b.UNITS if shared.search((PKG / "csrc" / u).read_text())]
+    assert "tree.hip" in units and len(units) >= 3, units
+    for u in units:
+        assert "-amdgpu-scalarize-global-loads=false" in b.UNITS[u], u
     llvm = "/opt/rocm/lib/llvm/bin"
-    obj = PKG / "build" / "tree.hip.o"
-    fat, co = tmp_path / "tree.fatbin", tmp_path / "tree.co"
-    subprocess.run([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", str(obj), str(tmp_path / "x.o")],
-                   check=True)
-    subprocess.run([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-    dis = subprocess.run([f"{llvm}/llvm-objdump", "-d", "--no-show-raw-insn", str(co)], check=True,
-                         capture_output=True, text=True).stdout
-    notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True,
-                           text=True).stdout
-    # the metadata map lists each kernel's keys in order: .kernarg_segment_size
-    # comes before .name
-    kernarg, size = {}, None
-    for ln in notes.splitlines():
-        if ".kernarg_segment_size:" in ln:
-            size = int(ln.split(":", 1)[1])
-        elif ".name:" in ln and size is not None:
-            kernarg[ln.split(":", 1)[1].strip()] = size
-            size = None
-    bodies, cur = {}, None
-    for ln in dis.splitlines():
-        if ln.endswith(">:"):
-            cur = ln.split("<", 1)[1].rstrip(">:")
-            bodies[cur] = []
-        elif cur:
-            bodies[cur].append(ln.strip())
+    kernarg, bodies = {}, {}
+    for u in units:
+        obj = PKG / "build" / (u + ".o")
+        fat, co = tmp_path / (u + ".fatbin"), tmp_path / (u + ".co")
+        subprocess.run([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", str(obj),
+                        str(tmp_path / "x.o")], check=True)
+        subprocess.run([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
+        dis = subprocess.run([f"{llvm}/llvm-objdump", "-d", "--no-show-raw-insn", str(co)], check=True,
+                             capture_output=True, text=True).stdout
+        notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True,
+                               text=True).stdout
+        # the metadata map lists each kernel's keys in order: .kernarg_segment_size
+        # comes before .name
+        size = None
+        for ln in notes.splitlines():
+            if ".kernarg_segment_size:" in ln:
+                size = int(ln.split(":", 1)[1])
+            elif ".name:" in ln and size is not None:
+                kernarg[ln.split(":", 1)[1].strip()] = size
+                size = None
+        cur = None
+        for ln in dis.splitlines():
+            if ln.endswith(">:"):
+                cur = ln.split("<", 1)[1].rstrip(">:")
+                bodies[cur] = []
+            elif cur:
+                bodies[cur].append(ln.strip())
     for key, single_base in (("6k_tree", True), ("11k_tree_wide", True), ("11k_tree_free", False)):
         sym = next(n for n in bodies if n.startswith(f"_ZN4oamd{key}E"))
         body = bodies[sym]

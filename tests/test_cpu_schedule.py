@@ -1,4 +1,4 @@
-"""The round schedule of k_tree's chain splitting (csrc/tree.hip, DESIGN.md §7
+"""The round schedule of k_tree's chain splitting (csrc/tree_search.h search_round, DESIGN.md §7
 "Exact endgames"), restated as a small model: per game, virtual threads are
 visited cyclically from the round's resume thread; a visit backs up the
 thread's waiting batch and selects, re-selecting at once while batches come

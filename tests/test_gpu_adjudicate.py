@@ -1,5 +1,5 @@
-"""Adjudication by the exact solver on the GPU (csrc/tree.hip
-selfplay_move_game / k_arena_move, csrc/adjudicate.hip): every stream is
+"""Adjudication by the exact solver on the GPU (csrc/tree_game.h
+selfplay_move_game, csrc/arena.hip k_arena_move, csrc/adjudicate.hip): every stream is
 replayed on the host with Position and othello_mcts.adjudicate, the three
 schedules of selfplay_steps against the move-by-move loop, the split solver
 against the plain one, the consumers, the arena, and the rows of inactive

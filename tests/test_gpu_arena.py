@@ -1,4 +1,4 @@
-"""On-device arena (othello_mcts.Arena, csrc/tree.hip k_arena_begin /
+"""On-device arena (othello_mcts.Arena, csrc/arena.hip k_arena_begin /
 k_arena_move) against the CPU reference match (tests/arena_ref.py), the fused
 call against the step-wise loop, and the per-game search mask."""
 

@@ -209,7 +209,7 @@ def _pos(b, g):
 @pytest.mark.parametrize("exact", [True, False], ids=["exact", "round_robin"])
 def test_evaluation_lists_through_endgames(om, exact):
     """The native search evaluates only the rows of non-terminal leaves (the
-    per-group evaluation lists of tree.hip append_rows, read by the ResNet
+    per-group evaluation lists of tree_search.h append_rows, read by the ResNet
     launch): through whole games, restarts and endgames full of terminal
     leaves it must give every game the same visits and Q as the callback path,
     which evaluates every row. 64 games = 2 pipeline groups of 1024-row

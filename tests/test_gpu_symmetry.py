@@ -3,7 +3,7 @@ evaluator that can see it (tests/asym_stub.py).
 
 Every other oracle / reference comparison of the search evaluates leaves with
 oracle.equivariant_stub or uniform_stub, for which the symmetry's three steps
-(the draw, csrc/rng.h draw_transform at csrc/tree.hip k_tree; the features
+(the draw, csrc/rng.h draw_transform at csrc/tree_search.h select_range; the features
 under t, inverse_transform in k_features_f32; the priors read back at
 transform_action(a, t) in expand_quads) cancel up to an ulp of fp32 summation
 order: a constant draw, a draw at the wrong event or a feature transform and a

@@ -4,10 +4,11 @@
 #   VARIANTS="name:extra flags[:SRC];name2:..." bash tools/variants.sh
 # SRC: empty = the tree's resnet.hip with the tree's other objects; + =
 # every unit of the working tree built with the flags;
-# a path = that resnet.hip with the tree's other objects; tree=PATH = that
-# tree.hip with the working tree's other units; @REV = all of
+# a path = that resnet.hip with the tree's other objects; @REV = all of
 # csrc/ and include/ at git revision REV (capi_net.hip packs the weights, so a
-# variant that changes the packing must bring its own C ABI units). The units and
+# variant that changes the packing must bring its own C ABI units; the search
+# tree is spread over several units and headers, so another tree is a revision
+# too). The units and
 # their flags are build.py's UNITS (resnet.hip's from RF). Built into
 # abv/<name>/liboamd.so (the pybind layer binds the C ABI, not the variant).
 set -eu
@@ -31,10 +32,9 @@ for e in "${SETS[@]}"; do
   mkdir -p abv/$name
   (
     set -e
-    dir=$CS inc="-I $CS -I include" every=1 rflags=$flags resnet= tree=
+    dir=$CS inc="-I $CS -I include" every=1 rflags=$flags resnet=
     case "${src:-}" in
       +) ;;                           # every unit of the working tree, built with the flags
-      tree=*) tree=${src#tree=} ;;    # another tree.hip, the working tree's other units
       @*)                             # every unit at a revision (the flags: its resnet.hip only)
         dir=abv/$name/src/$CS inc="-I $dir -I abv/$name/src/include" flags=
         mkdir -p abv/$name/src
@@ -47,7 +47,6 @@ for e in "${SETS[@]}"; do
       s=$dir/$unit f=$flags
       if [[ $unit == resnet.hip ]]; then s=${resnet:-$s} f=$rflags
       elif [[ $every == 0 ]]; then objs+=" $B/$unit.o"; continue
-      elif [[ $unit == tree.hip ]]; then s=${tree:-$s}
       fi
       [[ -f $s ]] || continue  # a revision from before the unit existed
       $CXX $inc $f $uflags -c $s -o abv/$name/$unit.o
