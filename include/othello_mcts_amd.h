@@ -659,6 +659,57 @@ int oamd_replay_relabel_endgames_split(const oamd_replay_view *view, int8_t *exa
                                        void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Baseline opponents: fixed classical players for the whole */
+/* game, in place of the reference's RandomPlayer, GreedyPlayer and          */
+/* EgaroucidPlayer (player.py:121-175, 262-321). A baseline gives every root */
+/* action of a position (0..63, or 64 when the mover must pass) one int32    */
+/* score for the side to move and picks one action with the maximal score.   */
+/*   RANDOM  every action scores 0                                            */
+/*   GREEDY  a square scores the discs it flips, the pass 0                   */
+/*   SEARCH  the exact negamax value `depth` disc placements deep (a pass     */
+/*           consumes none). A game that is over is worth 4096 sgn(d) + d, d  */
+/*           = mover's discs minus the other side's; a position at depth 0 is */
+/*           worth 10 (mobility) + 50 (corners) - 20 (X-squares beside an     */
+/*           empty corner) + discs, each as mover minus other side, |.| <     */
+/*           1000. With depth >= empties the scores are the exact solver's.   */
+/* Every move_scores entry that is no legal root action is                    */
+/* OAMD_BASELINE_NONE. score = the maximum; action = the lowest action with   */
+/* that score, or with a key the k-th lowest of the nt tied ones, k =         */
+/* min(nt - 1, (int)(u * nt)), u the first uniform of the random stream       */
+/* (key, event, 0): the argmax rule of the self-play move. A position where   */
+/* neither side can move has no action: every score OAMD_BASELINE_NONE,       */
+/* action -1, flags 0. A flagged position (OAMD_SOLVE_INVALID, or             */
+/* OAMD_SOLVE_NODE_LIMIT when a root action visited more than node_limit      */
+/* nodes) has the same outputs with its flags. nodes = positions visited      */
+/* plus static evaluations, summed over the root actions; 0 for RANDOM and    */
+/* GREEDY. legal_moves / next_legal_moves are ignored.                        */
+/* ------------------------------------------------------------------------ */
+#define OAMD_BASELINE_NONE INT32_MIN
+#define OAMD_BASELINE_RANDOM 0
+#define OAMD_BASELINE_GREEDY 1
+#define OAMD_BASELINE_SEARCH 2 /* depth in 1..10 */
+
+/* bytes of the caller-owned workspace for n positions */
+int oamd_baseline_workspace_bytes(int64_t n, int64_t *bytes);
+/* n positions on `device`. keys_dev / events_dev: (n) int64 each, or NULL (no
+ * keys: the lowest tied action; keys without events: event 0). Outputs
+ * (device, all required): move_scores_dev (n, 65) int32, score_dev, action_dev,
+ * flags_dev (n) int32, nodes_dev (n) int64. depth is read for SEARCH only;
+ * node_limit >= 1 is a budget per root action. workspace: caller-owned, size
+ * from oamd_baseline_workspace_bytes(n). workgroups = 0: a chip-filling grid;
+ * >= 1: that many 64-lane workgroups (no output depends on it). Enqueued
+ * only: allocates nothing, waits for nothing. */
+int oamd_baseline_moves(int32_t device, const oamd_position *pos_dev, int64_t n, int32_t kind, int32_t depth,
+                        int64_t node_limit, const int64_t *keys_dev, const int64_t *events_dev,
+                        int32_t *move_scores_dev, int32_t *score_dev, int32_t *action_dev, int32_t *flags_dev,
+                        int64_t *nodes_dev, void *workspace_dev, int32_t workgroups, void *stream);
+/* The same code on the host for one position (csrc/baseline.h). has_key = 0:
+ * key and event are ignored. Every output is required. */
+int oamd_host_baseline_move(const oamd_position *pos_host, int32_t kind, int32_t depth, int64_t node_limit,
+                            int32_t has_key, uint64_t key, uint64_t event, int32_t *move_scores65, int32_t *score,
+                            int32_t *action, int32_t *flags, int64_t *nodes);
+
+/* ------------------------------------------------------------------------ */
 /* Exact leaf values (opt-in, off by default): the search     */
 /* solves leaves with few empties instead of asking the net.                 */
 /* ------------------------------------------------------------------------ */

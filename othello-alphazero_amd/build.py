@@ -1,7 +1,8 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
   liboamd.so               HIP kernels (tree.hip, selfplay.hip, arena.hip over the headers wave.h, tree_search.h,
-                           tree_game.h; resnet.hip, replay.hip, solver.hip, adjudicate.hip, exact_leaves.hip)
+                           tree_game.h; resnet.hip, replay.hip, solver.hip, adjudicate.hip, exact_leaves.hip,
+                           baseline.hip)
                            + the C ABI
                            (capi.hip and, by subsystem, capi_net.hip, capi_play.hip, capi_data.hip; capi_version.hip
                            carries the source hashes), hipcc --offload-arch=gfx950
@@ -68,6 +69,10 @@ UNITS = {
     # exact leaf values: the solver's integer code on a 10-level
     # LDS stack; the build fails if a solve kernel reports any scratch
     "exact_leaves.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # baseline opponents: integer search on a 10-level LDS
+    # stack, the pick's one float product as rng.h needs it; the build fails if
+    # k_baseline reports any scratch
+    "baseline.hip": EXACT + ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 
@@ -179,9 +184,24 @@ def check_exact_leaves_scratch(remarks: str) -> None:
         raise SystemExit("build failed: no resource remark for k_solve_leaves in exact_leaves.hip")
 
 
+def check_baseline_scratch(remarks: str) -> None:
+    """baseline.hip: k_baseline keeps its searcher stack in LDS (20,480 bytes
+    per wave); fail on any scratch (k_baseline_pick holds no stack and is not
+    checked)."""
+    seen = 0
+    for name, field, value in kernel_remarks(remarks):
+        if "k_baseline" in name and "pick" not in name and field.startswith("ScratchSize"):
+            seen += 1
+            if int(value.split()[0]) != 0:
+                raise SystemExit(f"build failed: {name} uses {value} bytes of scratch per lane: "
+                                 "the baseline search's stack must stay in LDS")
+    if not seen:
+        raise SystemExit("build failed: no resource remark for k_baseline in baseline.hip")
+
+
 RESOURCE_CHECKS = {"resnet.hip": check_resnet, "solver.hip": check_solver_scratch}
 # units whose every search kernel must stay without scratch (its stack is LDS)
-SCRATCH_CHECKS = {"exact_leaves.hip": check_exact_leaves_scratch}
+SCRATCH_CHECKS = {"exact_leaves.hip": check_exact_leaves_scratch, "baseline.hip": check_baseline_scratch}
 
 
 def newer(out: Path, deps: list[Path]) -> bool:

@@ -1,6 +1,8 @@
-// C ABI, data: the packed replay ring, the exact endgame solver and the
-// relabelling of the ring's value targets. The caller owns every buffer.
+// C ABI, data: the packed replay ring, the exact endgame solver, the baseline
+// opponents and the relabelling of the ring's value targets. The caller owns
+// every buffer.
 
+#include "baseline.h"
 #include "capi_internal.h"
 
 using namespace oamd;
@@ -209,6 +211,63 @@ int oamd_host_solve_endgame_split(const oamd_position* pos_host, int32_t max_emp
     if (!pos_host || !move_scores65) return fail(OAMD_INVALID_ARGUMENT, "solve: position and move_scores are required");
     solve_host_split(pos_host->player, pos_host->player1_discs, pos_host->player2_discs, max_empties, node_limit,
                      move_scores65, score, best_action, flags, nodes);
+    return OAMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Baseline opponents (baseline.h, baseline.hip): the caller owns every buffer
+// ---------------------------------------------------------------------------
+static int baseline_checks(int32_t kind, int32_t depth, int64_t node_limit) {
+    if (kind < OAMD_BASELINE_RANDOM || kind > OAMD_BASELINE_SEARCH)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected a baseline kind in 0..2, but got " + std::to_string(kind) + ".");
+    if (kind == OAMD_BASELINE_SEARCH && (depth < 1 || depth > kBaselineMaxDepth))
+        return fail(OAMD_INVALID_ARGUMENT, "Expected 1 <= depth <= " + std::to_string(kBaselineMaxDepth) +
+                                               ", but got " + std::to_string(depth) + ".");
+    if (node_limit < 1 || node_limit >= (1LL << kSolveStatusShift))
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "Expected 1 <= node_limit < 2^56, but got " + std::to_string(node_limit) + ".");
+    return OAMD_OK;
+}
+
+int oamd_baseline_workspace_bytes(int64_t n, int64_t* bytes) {
+    if (int rc = bytes_check(bytes, "baseline")) return rc;
+    if (int rc = solve_n_check(n)) return rc;
+    *bytes = baseline_workspace_bytes(n);
+    return OAMD_OK;
+}
+
+int oamd_baseline_moves(int32_t device, const oamd_position* pos_dev, int64_t n, int32_t kind, int32_t depth,
+                        int64_t node_limit, const int64_t* keys_dev, const int64_t* events_dev,
+                        int32_t* move_scores_dev, int32_t* score_dev, int32_t* action_dev, int32_t* flags_dev,
+                        int64_t* nodes_dev, void* workspace_dev, int32_t workgroups, void* stream) {
+    if (int rc = baseline_checks(kind, depth, node_limit)) return rc;
+    if (int rc = solve_n_check(n)) return rc;
+    if (workgroups < 0)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected workgroups >= 0, but got " + std::to_string(workgroups) + ".");
+    if (!move_scores_dev || !score_dev || !action_dev || !flags_dev || !nodes_dev)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "baseline: move_scores, score, action, flags and nodes output buffers are required");
+    if (!has_device(device)) return fail(OAMD_INVALID_ARGUMENT, "baseline: no HIP device " + std::to_string(device));
+    if (n == 0) return OAMD_OK;
+    if (!pos_dev || !workspace_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "baseline: positions and workspace buffers are required");
+    DeviceGuard dg(device);
+    int cus = 0;
+    if (int rc = device_cus(device, &cus)) return rc;
+    launch_baseline(pos_dev, n, kind, depth, node_limit, keys_dev, events_dev, move_scores_dev, score_dev, action_dev,
+                    flags_dev, nodes_dev, workspace_dev, workgroups, cus, (hipStream_t)stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+int oamd_host_baseline_move(const oamd_position* pos_host, int32_t kind, int32_t depth, int64_t node_limit,
+                            int32_t has_key, uint64_t key, uint64_t event, int32_t* move_scores65, int32_t* score,
+                            int32_t* action, int32_t* flags, int64_t* nodes) {
+    if (int rc = baseline_checks(kind, depth, node_limit)) return rc;
+    if (!pos_host || !move_scores65 || !score || !action || !flags || !nodes)
+        return fail(OAMD_INVALID_ARGUMENT, "baseline: the position and every output are required");
+    baseline_host(pos_host->player, pos_host->player1_discs, pos_host->player2_discs, kind, depth, node_limit,
+                  has_key != 0, key, event, move_scores65, score, action, flags, nodes);
     return OAMD_OK;
 }
 

@@ -1018,6 +1018,37 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
                                            st));
     });
 
+    // ---- baseline opponents (othello_mcts/baseline.py) ----
+    m.def("_host_baseline", [](int player, uint64_t p1, uint64_t p2, int kind, int depth, int64_t node_limit,
+                               bool has_key, uint64_t key, uint64_t event) {
+        oamd_position p{};
+        p.player = player;
+        p.player1_discs = p1;
+        p.player2_discs = p2;
+        int32_t ms[65], score = 0, action = 0, flags = 0;
+        int64_t nodes = 0;
+        check(oamd_host_baseline_move(&p, kind, depth, node_limit, has_key ? 1 : 0, key, event, ms, &score, &action,
+                                      &flags, &nodes));
+        return py::make_tuple(std::vector<int>(ms, ms + 65), score, action, flags, nodes);
+    });
+    m.def("_baseline_workspace_bytes", [](int64_t n) {
+        int64_t bytes = 0;
+        check(oamd_baseline_workspace_bytes(n, &bytes));
+        return bytes;
+    });
+    // keys / events: device pointers or 0
+    m.def("_gpu_baseline", [](int device, uintptr_t pos, int64_t n, int kind, int depth, int64_t node_limit,
+                              uintptr_t keys, uintptr_t events, uintptr_t move_scores, uintptr_t score,
+                              uintptr_t action, uintptr_t flags, uintptr_t nodes, uintptr_t workspace, int workgroups,
+                              uintptr_t stream) {
+        check(oamd_baseline_moves(device, reinterpret_cast<const oamd_position*>(pos), n, kind, depth, node_limit,
+                                  reinterpret_cast<const int64_t*>(keys), reinterpret_cast<const int64_t*>(events),
+                                  reinterpret_cast<int32_t*>(move_scores), reinterpret_cast<int32_t*>(score),
+                                  reinterpret_cast<int32_t*>(action), reinterpret_cast<int32_t*>(flags),
+                                  reinterpret_cast<int64_t*>(nodes), reinterpret_cast<void*>(workspace), workgroups,
+                                  reinterpret_cast<void*>(stream)));
+    });
+
     // the split solver: the same convention
     m.def("_gpu_solve_split", [](int device, uintptr_t pos, int64_t n, int max_empties, int64_t node_limit,
                                  uintptr_t move_scores, uintptr_t score, uintptr_t best, uintptr_t flags,

@@ -27,6 +27,9 @@ full searches and policy target pruning (``prune_visit_counts`` is the pruning
 rule on the host). ``BatchedMCTS.set_exact_leaves`` makes the search solve
 leaves with few empties instead of asking the net (``exact_leaf_value`` is the
 rule on the host, ``exact_leaf_values`` the solve kernel's path on the GPU).
+``baseline_moves`` / ``baseline_move`` are fixed classical opponents (random,
+greedy, a depth-limited alpha-beta search; GPU and host) and ``Gauntlet`` plays
+G matches of one net against one of them.
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -54,6 +57,7 @@ from .selfplay import FIN_FAST, SelfPlayCollector, self_play  # noqa: E402,F401
 from .replay import ReplayBuffer  # noqa: E402,F401
 from .endgame import EndgameSolution, endgame_move_loss, solve_endgames, solve_position  # noqa: E402,F401
 from .adjudication import adjudicate  # noqa: E402,F401
+from .baseline import BaselineMoves, Gauntlet, baseline_move, baseline_moves  # noqa: E402,F401
 from .exact_leaves import exact_leaf_value, exact_leaf_values  # noqa: E402,F401
 from .training import (  # noqa: E402,F401
     SampleBuffer,
@@ -93,4 +97,8 @@ __all__ = [
     "prune_visit_counts",
     "exact_leaf_value",
     "exact_leaf_values",
+    "BaselineMoves",
+    "Gauntlet",
+    "baseline_move",
+    "baseline_moves",
 ]

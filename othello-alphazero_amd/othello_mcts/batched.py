@@ -68,6 +68,8 @@ class BatchedMCTS:
         self._margin = None
         self._C = C
         self.exact_leaves = 0  # set_exact_leaves
+        self.playout_cap = None  # set_playout_cap: (full_probability, fast_simulations)
+        self.forced_playouts = None  # set_forced_playouts: (k, prune_targets)
 
     @property
     def rows_per_step(self) -> int:
@@ -150,6 +152,7 @@ class BatchedMCTS:
         The arena does not use the setting and rejects an engine that has it."""
         if full_probability is None and fast_simulations is None:
             self.engine.set_playout_cap(1.0, 0)
+            self.playout_cap = None
             return
         if full_probability is None or fast_simulations is None:
             raise ValueError("Expected full_probability and fast_simulations together (or neither: off).")
@@ -160,6 +163,7 @@ class BatchedMCTS:
             raise ValueError(f"Expected 1 <= fast_simulations <= num_simulations ({self.config.num_simulations}), "
                              f"but got {fast_simulations}.")
         self.engine.set_playout_cap(p, n)
+        self.playout_cap = (p, n)
 
     def set_forced_playouts(self, k: float | None = None, prune_targets: bool = True) -> None:
         """Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2;
@@ -177,11 +181,13 @@ class BatchedMCTS:
         The arena does not use the setting and rejects an engine that has it."""
         if k is None:
             self.engine.set_forced_playouts(0.0, False)
+            self.forced_playouts = None
             return
         kf = float(k)
         if not (math.isfinite(kf) and kf > 0.0):
             raise ValueError(f"Expected a finite forced playout factor k > 0, but got {k}.")
         self.engine.set_forced_playouts(kf, bool(prune_targets))
+        self.forced_playouts = (kf, bool(prune_targets))
 
     def set_exact_leaves(self, max_empties: int | None = None) -> None:
         """Exact leaf values. With ``max_empties = E`` in 1..10 a
