@@ -425,6 +425,85 @@ int oamd_engine_game_event(oamd_engine *e, int32_t game, uint64_t *event_host);
 int oamd_engine_set_active(oamd_engine *e, const uint8_t *active_dev);
 
 /* ------------------------------------------------------------------------ */
+/* Search from given positions: a root set from outside and  */
+/* the principal variation below a searched root. The counterpart of         */
+/* MCTS::reset_position (mcts.cpp:40-43) for a position that is not the      */
+/* initial one; the reference has no such entry point.                       */
+/* ------------------------------------------------------------------------ */
+
+/* The canonical form of a position, from its player and two disc sets alone
+ * (the other fields of *in_host are not read): legal_moves and
+ * next_legal_moves as Position::apply_action would have left them; a side to
+ * move that has no move while the opponent has one stays to move (a pass
+ * position: legal_moves 0, next_legal_moves the opponent's moves, action 64
+ * legal); player 1 or 2 where neither side has a move becomes terminal
+ * (player 0), and a terminal position has no moves. The same code runs on
+ * the device in oamd_engine_set_positions (csrc/positions.h).
+ * OAMD_INVALID_ARGUMENT: player outside 0..2 or overlapping disc sets. */
+int oamd_host_canonical_position(const oamd_position *in_host, oamd_position *out_host);
+
+/* status_dev values of oamd_engine_set_positions */
+#define OAMD_SET_POSITIONS_OK 0
+#define OAMD_SET_POSITIONS_SKIPPED (-1)           /* the mask left the game alone */
+#define OAMD_SET_POSITIONS_BAD_PLAYER 1           /* player outside 0..2 */
+#define OAMD_SET_POSITIONS_OVERLAP 2              /* a square holds a disc of both colours */
+#define OAMD_SET_POSITIONS_HISTORY_BAD_PLAYER 3   /* ... in one of the game's used history entries */
+#define OAMD_SET_POSITIONS_HISTORY_OVERLAP 4
+#define OAMD_SET_POSITIONS_BAD_HIST_LEN 5         /* hist_len outside 0..history_k */
+#define OAMD_SET_POSITIONS_BAD_PLY 6              /* ply < 0 */
+#define OAMD_SET_POSITIONS_CAPACITY 7             /* node_capacity < hist_len + 1 */
+
+/* Put a position at the root of every selected game. All pointers are device
+ * pointers with one entry per game of the engine (G); all but pos_dev may be
+ * NULL.
+ *   pos_dev (G): the roots. Only player and the two disc sets are read; the
+ *     engine stores the canonical form (oamd_host_canonical_position), so a
+ *     position whose sides both have no move is a terminal root.
+ *   history_dev (G, history_k), history_k in 0..15: the positions before the
+ *     root, newest first (entry 0 is the root's parent). They fill the history
+ *     planes of every feature row and self-play target below this root, as the
+ *     game's own earlier roots do; nothing checks that they form a legal game.
+ *   hist_len_dev (G), each in 0..history_k: the used entries of each game;
+ *     NULL = history_k for every game. Planes past them are zero, as for a
+ *     game with fewer moves than history_size (position_iterator.h:24-71).
+ *   keys_dev (G): the games' random-stream keys; NULL = the key
+ *     oamd_engine_reset(e, game, seed) gives. `seed` is not read otherwise.
+ *   ply_dev (G), each >= 0: the moves played so far, which the self-play move's
+ *     temperature schedule and the playout cap's draw read; NULL = discs on
+ *     the board - 4.
+ *   mask_dev (G) bytes: nonzero = set this game; NULL = every game.
+ *   status_dev (G) out: OAMD_SET_POSITIONS_OK for a game that was set,
+ *     _SKIPPED for one the mask left alone, else the fault (the first of: the
+ *     root's, hist_len, ply, capacity, the history's from the newest entry on).
+ * A game that is set is as after oamd_engine_reset (a fresh node pool, active,
+ * event 0, no arena match, sticky flags cleared) with this root, key and ply.
+ * A rejected game is left exactly as it was. Enqueued on the engine's stream;
+ * the host does not wait. For the exact-leaf setting (below) the call counts as
+ * a reset of the games it sets, one by one: it does not lift the restriction
+ * on changing max_empties, which only a reset of all games lifts.
+ * OAMD_INVALID_ARGUMENT: pos_dev NULL, history_k outside 0..15, history_dev
+ * NULL with history_k > 0. */
+int oamd_engine_set_positions(oamd_engine *e, const oamd_position *pos_dev, const oamd_position *history_dev,
+                              int32_t history_k, const int32_t *hist_len_dev, const uint64_t *keys_dev,
+                              const int32_t *ply_dev, const uint8_t *mask_dev, uint64_t seed, int32_t *status_dev);
+
+/* The principal variation of every game's tree, read on the device after a
+ * search: from the root, the child with the most visits (of equally visited
+ * children the first in legal_actions() order, i.e. the lowest action), then
+ * the same below that child, until a node has no children (unexpanded,
+ * terminal, or an exact leaf), its best child has no visit, or max_len (1..64)
+ * entries are written. Device outputs:
+ *   pv_actions_dev (G, max_len) int32: the actions, -1 past the end;
+ *   pv_visits_dev (G, max_len) int32 and pv_q_dev (G, max_len) fp32: N and Q
+ *     of each chosen child, as oamd_engine_root_stats reports the children of
+ *     the node they hang from (the same sign convention), 0 past the end;
+ *   pv_len_dev (G) int32: the entries written; 0 for an inactive game.
+ * Enqueued only; reads the trees, changes nothing.
+ * OAMD_INVALID_ARGUMENT: max_len outside 1..64 or a NULL output. */
+int oamd_engine_principal_variations(oamd_engine *e, int32_t max_len, int32_t *pv_actions_dev,
+                                     int32_t *pv_visits_dev, float *pv_q_dev, int32_t *pv_len_dev);
+
+/* ------------------------------------------------------------------------ */
 /* Arena: G head-to-head matches between two nets, all on the device.        */
 /* Replaces play_game between two AlphaZeroPlayers (player.py:33-95,         */
 /* 177-259) as evaluation.py:15-90 runs it. Match g is game g of engine a     */
@@ -736,7 +815,9 @@ int oamd_host_baseline_move(const oamd_position *pos_host, int32_t kind, int32_t
  * setting. The value may change only while no game holds a tree built under
  * another value, i.e. before the first search or after oamd_engine_reset of
  * all games (game = -1) or oamd_engine_random_openings: OAMD_INVALID_ARGUMENT
- * otherwise, and for E outside 0..10. Independent of the playout cap, forced
+ * otherwise, and for E outside 0..10. oamd_engine_set_positions counts as a
+ * reset of each game it sets, like oamd_engine_reset with game >= 0: the host
+ * does not learn which games were rejected, so it never lifts the restriction. Independent of the playout cap, forced
  * playouts and adjudication. The arena rejects an engine that has it. */
 int oamd_engine_set_exact_leaves(oamd_engine *e, int32_t max_empties);
 /* Since the engine was created (host outputs; waits for the engine's stream):

@@ -1,7 +1,7 @@
 """Build the MI355X-native othello_mcts extension in-tree.
 
-  liboamd.so               HIP kernels (tree.hip, selfplay.hip, arena.hip over the headers wave.h, tree_search.h,
-                           tree_game.h; resnet.hip, replay.hip, solver.hip, adjudicate.hip, exact_leaves.hip,
+  liboamd.so               HIP kernels (tree.hip, selfplay.hip, arena.hip, positions.hip over the headers wave.h,
+                           tree_search.h, tree_game.h; resnet.hip, replay.hip, solver.hip, adjudicate.hip, exact_leaves.hip,
                            baseline.hip)
                            + the C ABI
                            (capi.hip and, by subsystem, capi_net.hip, capi_play.hip, capi_data.hip; capi_version.hip
@@ -43,7 +43,7 @@ EXACT = ["-ffp-contract=off", "-fno-fast-math"]
 # see those stores (tests/test_cpu_host.py checks the ISA)
 NO_SCALAR_LOADS = ["-mllvm", "-amdgpu-scalarize-global-loads=false"]
 # every unit that includes tree_search.h or tree_game.h is built this way
-TREE_UNITS = ("tree.hip", "selfplay.hip", "arena.hip")
+TREE_UNITS = ("tree.hip", "selfplay.hip", "arena.hip", "positions.hip")
 UNITS = {
     **{u: EXACT + NO_SCALAR_LOADS for u in TREE_UNITS},
     "capi.hip": EXACT,

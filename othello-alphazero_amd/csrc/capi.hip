@@ -13,6 +13,7 @@
 #include "capi_internal.h"
 #include "exact_leaf.h"
 #include "forced.h"
+#include "positions.h"
 #include "rng.h"
 
 using namespace oamd;
@@ -1268,6 +1269,50 @@ int oamd_engine_game_event(oamd_engine* e, int32_t game, uint64_t* event) {
 int oamd_engine_set_active(oamd_engine* e, const uint8_t* active_dev) {
     DeviceGuard dg(e->device);
     launch_set_active(e->view(), active_dev, e->stream);
+    LAUNCHCHK();
+    return OAMD_OK;
+}
+
+// ------------------------------------------- given positions
+int oamd_host_canonical_position(const oamd_position* in, oamd_position* out) {
+    if (!in || !out) return fail(OAMD_INVALID_ARGUMENT, "canonical_position: null position");
+    const int32_t f = position_fault(in->player, in->player1_discs, in->player2_discs);
+    if (f == kSetPosBadPlayer)
+        return fail(OAMD_INVALID_ARGUMENT, "Expected player in {0, 1, 2}, but got " + std::to_string(in->player) + ".");
+    if (f) return fail(OAMD_INVALID_ARGUMENT, "The two players' disc sets overlap.");
+    const Pos c = canonical_position(in->player, in->player1_discs, in->player2_discs);
+    std::memcpy(out, &c, sizeof(Pos));
+    return OAMD_OK;
+}
+
+int oamd_engine_set_positions(oamd_engine* e, const oamd_position* pos_dev, const oamd_position* history_dev,
+                              int32_t history_k, const int32_t* hist_len_dev, const uint64_t* keys_dev,
+                              const int32_t* ply_dev, const uint8_t* mask_dev, uint64_t seed, int32_t* status_dev) {
+    if (!pos_dev) return fail(OAMD_INVALID_ARGUMENT, "set_positions: pos_dev is NULL");
+    if (history_k < 0 || history_k > kMaxHistory)
+        return fail(OAMD_INVALID_ARGUMENT, "set_positions: Expected 0 <= history_k <= " + std::to_string(kMaxHistory) +
+                                               ", but got " + std::to_string(history_k) + ".");
+    if (history_k > 0 && !history_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "set_positions: history_dev is NULL with history_k > 0");
+    DeviceGuard dg(e->device);
+    launch_set_positions(e->view(), pos_dev, history_dev, history_k, hist_len_dev, keys_dev, ply_dev, mask_dev, seed,
+                         status_dev, e->stream);
+    LAUNCHCHK();
+    // a reset of single games: no step-wise search stays open, and exact_trees
+    // stays as it is (a rejected game keeps its tree, and nobody waited to know)
+    e->end_search();
+    return OAMD_OK;
+}
+
+int oamd_engine_principal_variations(oamd_engine* e, int32_t max_len, int32_t* pv_actions_dev, int32_t* pv_visits_dev,
+                                     float* pv_q_dev, int32_t* pv_len_dev) {
+    if (max_len < 1 || max_len > 64)
+        return fail(OAMD_INVALID_ARGUMENT,
+                    "principal_variations: Expected 1 <= max_len <= 64, but got " + std::to_string(max_len) + ".");
+    if (!pv_actions_dev || !pv_visits_dev || !pv_q_dev || !pv_len_dev)
+        return fail(OAMD_INVALID_ARGUMENT, "principal_variations: null output buffer");
+    DeviceGuard dg(e->device);
+    launch_principal_variations(e->view(), max_len, pv_actions_dev, pv_visits_dev, pv_q_dev, pv_len_dev, e->stream);
     LAUNCHCHK();
     return OAMD_OK;
 }

@@ -74,6 +74,18 @@ void launch_flips(const uint64_t* mv, const uint64_t* me, const uint64_t* opp, u
 void launch_apply_positions(const Pos* in, const int32_t* actions, Pos* out, int64_t n,
                             hipStream_t s);
 
+// positions.hip. set_positions: game g takes pos[g] as its root
+// behind hist_len[g] (nullptr: K) of its K ancestors history[g * K ..], newest
+// first; keys / ply / mask may be nullptr (the key of a reset with `seed`,
+// discs - 4, every game); status[g] = 0, -1 (not selected) or the fault of a
+// rejected game, which is left as it was. principal_variations: the most
+// visited line below every root, (G, max_len) outputs and (G) lengths.
+void launch_set_positions(const EngineView& E, const oamd_position* pos, const oamd_position* history, int K,
+                          const int32_t* hist_len, const uint64_t* keys, const int32_t* ply, const uint8_t* mask,
+                          uint64_t seed, int32_t* status, hipStream_t s);
+void launch_principal_variations(const EngineView& E, int max_len, int32_t* pv_actions, int32_t* pv_visits,
+                                 float* pv_q, int32_t* pv_len, hipStream_t s);
+
 // arena.hip (k_arena_begin / k_arena_move): match g = game g of engines A
 // and B (same G). begin resets both games, plays the opening plies in both
 // trees and activates the side to move; move plays one ply of every match;

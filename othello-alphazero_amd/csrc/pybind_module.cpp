@@ -478,6 +478,16 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
           "k"_a = 2.0f);
     m.def("set_resnet_c128_four_wave", [](bool enable) { check(oamd_set_resnet_c128_four_wave(enable ? 1 : 0)); });
     m.def("resnet_c128_four_wave", []() { return oamd_resnet_c128_four_wave() != 0; });
+    // the canonical form of (player, player1_discs, player2_discs) (csrc/positions.h)
+    m.def("_canonical_position", [](int player, uint64_t p1, uint64_t p2) {
+        oamd_position in{};
+        in.player = player;
+        in.player1_discs = p1;
+        in.player2_discs = p2;
+        Position out;
+        check(oamd_host_canonical_position(&in, &out.p));
+        return out;
+    });
     m.def("source_hash", [](const std::string& family) {
         const char* h = oamd_source_hash(family.c_str());
         if (!h) throw py::value_error("unknown source family: " + family);
@@ -763,6 +773,22 @@ PYBIND11_MODULE(_othello_mcts_impl, m) {
         .def("set_active",
              [](Engine& e, uintptr_t active) {
                  check(oamd_engine_set_active(e.h, reinterpret_cast<const uint8_t*>(active)));
+             })
+        // device pointers, 0 = NULL (include/othello_mcts_amd.h: given positions)
+        .def("set_positions",
+             [](Engine& e, uintptr_t pos, uintptr_t history, int history_k, uintptr_t hist_len, uintptr_t keys,
+                uintptr_t ply, uintptr_t mask, uint64_t seed, uintptr_t status) {
+                 check(oamd_engine_set_positions(
+                     e.h, reinterpret_cast<const oamd_position*>(pos), reinterpret_cast<const oamd_position*>(history),
+                     history_k, reinterpret_cast<const int32_t*>(hist_len), reinterpret_cast<const uint64_t*>(keys),
+                     reinterpret_cast<const int32_t*>(ply), reinterpret_cast<const uint8_t*>(mask), seed,
+                     reinterpret_cast<int32_t*>(status)));
+             })
+        .def("principal_variations",
+             [](Engine& e, int max_len, uintptr_t actions, uintptr_t visits, uintptr_t q, uintptr_t len) {
+                 check(oamd_engine_principal_variations(e.h, max_len, reinterpret_cast<int32_t*>(actions),
+                                                        reinterpret_cast<int32_t*>(visits),
+                                                        reinterpret_cast<float*>(q), reinterpret_cast<int32_t*>(len)));
              })
         // arena (othello_mcts/arena.py): self = engine A, other = engine B
         .def("arena_begin",

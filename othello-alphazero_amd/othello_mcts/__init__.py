@@ -29,7 +29,11 @@ leaves with few empties instead of asking the net (``exact_leaf_value`` is the
 rule on the host, ``exact_leaf_values`` the solve kernel's path on the GPU).
 ``baseline_moves`` / ``baseline_move`` are fixed classical opponents (random,
 greedy, a depth-limited alpha-beta search; GPU and host) and ``Gauntlet`` plays
-G matches of one net against one of them.
+G matches of one net against one of them. ``BatchedMCTS.set_positions`` puts
+given positions (with their history) at the roots, ``principal_variations``
+reads the most visited lines on the device, and ``analyze`` takes any list of
+positions through an engine (``parse_board`` / ``format_board`` for board
+strings, ``canonical_position`` is the stored form on the host).
 
 There is no CPU fallback: importing works anywhere the extension was built,
 but creating a search object needs a ROCm GPU and raises otherwise.
@@ -59,6 +63,7 @@ from .endgame import EndgameSolution, endgame_move_loss, solve_endgames, solve_p
 from .adjudication import adjudicate  # noqa: E402,F401
 from .baseline import BaselineMoves, Gauntlet, baseline_move, baseline_moves  # noqa: E402,F401
 from .exact_leaves import exact_leaf_value, exact_leaf_values  # noqa: E402,F401
+from .analysis import Analysis, analyze, canonical_position, format_board, parse_board, position_key  # noqa: E402,F401
 from .training import (  # noqa: E402,F401
     SampleBuffer,
     alphazero_loss,
@@ -101,4 +106,10 @@ __all__ = [
     "Gauntlet",
     "baseline_move",
     "baseline_moves",
+    "Analysis",
+    "analyze",
+    "canonical_position",
+    "parse_board",
+    "format_board",
+    "position_key",
 ]

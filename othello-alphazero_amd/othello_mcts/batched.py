@@ -140,6 +140,103 @@ class BatchedMCTS:
             raise ValueError(f"Expected {self.num_games} mask entries, but got shape {tuple(m.shape)}.")
         self.engine.set_active(m.data_ptr())
 
+    def set_positions(self, positions, history=None, ply=None, keys=None, games=None, seed: int = 0) -> None:
+        """Put given positions at the roots of games.
+
+        ``positions``: an ``(n, 5)`` int64 tensor in ``pack_positions`` layout or a
+        sequence of ``Position`` objects / ``(player, player1_discs,
+        player2_discs)`` triples; entry i goes to game ``games[i]`` (default
+        ``range(n)``, n <= G). Only the player and the two disc sets are read: the
+        engine stores ``canonical_position`` of each. ``history``: the positions
+        before each root, newest first, as ``(n, K, 5)`` or as a list of
+        per-position lists of unequal length (K <= 15); they fill the history
+        planes as the game's own earlier roots would. ``ply``: moves played so
+        far (default: discs - 4), read by the self-play move's temperature
+        schedule and the playout cap. ``keys``: the games' random-stream keys
+        (default: the keys ``reset(game, seed)`` gives).
+
+        A game that is set is as after ``reset``: a fresh tree, active, event 0.
+        Waits for the engine's stream to read the status back; raises ValueError
+        naming the first rejected entry and its fault. Rejected games are left as
+        they were, and the accepted games of the same call stay set."""
+        from .analysis import pack_history, pack_position_rows, set_positions_fault
+
+        G = self.num_games
+        self._stream()
+        rows = pack_position_rows(positions)
+        n = rows.shape[0]
+        if games is None:
+            games = list(range(n))
+        games = [int(g) for g in games]
+        if len(games) != n:
+            raise ValueError(f"Expected {n} game indices, but got {len(games)}.")
+        if n > G or len(set(games)) != n or any(not 0 <= g < G for g in games):
+            raise ValueError(f"Expected at most {G} distinct games in [0, {G}), but got {games}.")
+        idx = torch.tensor(games, dtype=torch.int64)
+        pos = torch.zeros((G, 5), dtype=torch.int64)
+        pos[idx] = rows
+        mask = torch.zeros(G, dtype=torch.uint8)
+        mask[idx] = 1
+        dev = self.device
+        hist_d = len_d = ply_d = keys_d = None
+        K = 0
+        if history is not None:
+            hist_n, lens = pack_history(history, n)
+            K = hist_n.shape[1]
+            if K > 0:
+                hist = torch.zeros((G, K, 5), dtype=torch.int64)
+                hist[idx] = hist_n
+                hl = torch.zeros(G, dtype=torch.int32)
+                hl[idx] = lens
+                hist_d, len_d = hist.to(dev), hl.to(dev)
+        if ply is not None:
+            pl = torch.zeros(G, dtype=torch.int32)
+            pl[idx] = torch.as_tensor(ply).to("cpu", torch.int32).reshape(n)
+            ply_d = pl.to(dev)
+        if keys is not None:
+            if isinstance(keys, torch.Tensor):
+                kn = keys.to("cpu", torch.int64).reshape(n)
+            else:
+                kn = torch.tensor([(int(k) & 0xFFFFFFFFFFFFFFFF) - ((int(k) & (1 << 63)) << 1) for k in keys],
+                                  dtype=torch.int64).reshape(n)
+            kk = torch.zeros(G, dtype=torch.int64)
+            kk[idx] = kn
+            keys_d = kk.to(dev)
+        pos_d, mask_d = pos.to(dev), mask.to(dev)
+        status = torch.empty(G, dtype=torch.int32, device=dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        self.engine.set_positions(pos_d.data_ptr(), ptr(hist_d), K, ptr(len_d), ptr(keys_d), ptr(ply_d),
+                                  mask_d.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, status.data_ptr())
+        st = status.cpu()[idx]  # the host wait: the inputs above outlive the kernel
+        bad = torch.nonzero(st != 0).reshape(-1)
+        if bad.numel():
+            i = int(bad[0])
+            raise ValueError(f"set_positions: entry {i} (game {games[i]}) was rejected: "
+                             f"{set_positions_fault(int(st[i]))}"
+                             + (f" ({bad.numel()} entries rejected in all)" if bad.numel() > 1 else "") + ".")
+
+    def principal_variations(self, max_len: int = 16) -> dict[str, torch.Tensor]:
+        """The most visited line below every root, read on the device (DESIGN.md
+        §22): from the root the child with the most visits, the lowest action
+        among equals, then the same below it, until a node without children, a
+        best child without a visit or ``max_len`` (1..64) entries. Device
+        tensors: ``actions`` (G, max_len) int32 padded with -1, ``visits``
+        (G, max_len) int32 and ``q`` (G, max_len) fp32 of the chosen children
+        (as ``root_stats`` reports a root's), ``length`` (G) int32, 0 for an
+        inactive game. Enqueued only."""
+        max_len = int(max_len)
+        if not 1 <= max_len <= 64:
+            raise ValueError(f"Expected 1 <= max_len <= 64, but got {max_len}.")
+        self._stream()
+        G, d = self.num_games, self.device
+        out = {"actions": torch.empty((G, max_len), dtype=torch.int32, device=d),
+               "visits": torch.empty((G, max_len), dtype=torch.int32, device=d),
+               "q": torch.empty((G, max_len), dtype=torch.float32, device=d),
+               "length": torch.empty(G, dtype=torch.int32, device=d)}
+        self.engine.principal_variations(max_len, out["actions"].data_ptr(), out["visits"].data_ptr(),
+                                         out["q"].data_ptr(), out["length"].data_ptr())
+        return out
+
     def set_playout_cap(self, full_probability: float | None = None, fast_simulations: int | None = None) -> None:
         """Playout cap randomization (KataGo, Wu 2019, section 3.1).
         With a cap set, a game's search at a given ply is a full one

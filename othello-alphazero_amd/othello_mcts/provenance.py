@@ -18,12 +18,12 @@ INCLUDE = Path(__file__).resolve().parent.parent.parent / "include"
 # the sources each kernel family is compiled from
 FAMILIES = {
     "resnet": ["resnet.hip", "kernels.h"],
-    "tree": ["tree.hip", "selfplay.hip", "arena.hip", "wave.h", "tree_search.h", "tree_game.h", "engine.h",
+    "tree": ["tree.hip", "selfplay.hip", "arena.hip", "positions.hip", "positions.h", "wave.h", "tree_search.h", "tree_game.h", "engine.h",
              "bitboard.h", "rng.h", "forced.h", "exact_leaf.h", "solver.h", "kernels.h",
              "../../include/othello_mcts_amd.h"],
     "all": ["adjudicate.hip", "arena.hip", "baseline.h", "baseline.hip", "bitboard.h", "capi.hip", "capi_data.hip", "capi_internal.h",
             "capi_net.hip", "capi_play.hip", "capi_version.hip", "engine.h", "exact_leaf.h", "exact_leaves.hip",
-            "forced.h", "host_resources.h", "kernels.h", "replay.h", "replay.hip", "resnet.hip", "rng.h",
+            "forced.h", "host_resources.h", "kernels.h", "positions.h", "positions.hip", "replay.h", "replay.hip", "resnet.hip", "rng.h",
             "schedule.h", "selfplay.hip", "solver.h", "solver.hip", "timing.h", "tree.hip", "tree_game.h",
             "tree_search.h", "wave.h",
             "../../include/othello_mcts_amd.h", "../../include/othello_mcts_amd_experimental.h"],
